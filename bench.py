@@ -24,7 +24,16 @@ north_star's "final RCCL gather"), outside `value` (--no-gather skips it).
 `--gpus N` outside a launcher starts the N ranks itself (torch.distributed.run
 as a child process); under a launcher, WORLD_SIZE must equal N.
 
+A plain run sets up, warms up, times the K steps and prints the line.  The
+passes that measure something else than `value` run only with --full: the
+per-step distribution (50 more steps), the input-reading companion, the
+end-to-end pass from a WAV in host memory and the CPU baseline; without it
+their fields in the line are null.  --dump-outputs DIR writes what the last
+timed step computed as DIR/<name>.npy (the inputs are seeded: the same
+arguments give the same files from every build that computes the same).
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--minutes M]
+                       [--full] [--dump-outputs DIR]
                        [--no-cpu-baseline] [--no-gather]
 """
 from __future__ import annotations
@@ -56,6 +65,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--minutes", type=float, default=60.0, help="audio per GPU (default 1 h)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the passes that are not the line's value: the per-step "
+                         "distribution, the input-reading companion, the end-to-end pass and the CPU baseline "
+                         "(each has its own --no-... switch); without it the line carries null for them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (the render, the spectra, "
+                         "...) as DIR/<name>.npy, float32: whole arrays where they are small, else a head, a tail "
+                         "and a fixed seeded sample of each (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget")
     ap.add_argument("--no-gather", action="store_true",
@@ -357,6 +374,41 @@ def cpu_baseline(seconds_budget: float):
                       "STFT (oracle/oracle.c, OpenMP over frames). CPU restatement, not IPP"}
 
 
+DUMP_BUDGET = 48 << 20  # bytes of .npy payload over all ranks (--dump-outputs may write 64 MB)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(dirname: str, arrays: dict, world: int = 1, rank: int = 0):
+    """--dump-outputs: the tensors a caller of the timed path receives, as they
+    stand after the last timed step, as float32 DIR/<name>.npy (with
+    _rank<r> after the name at N > 1).  An array within its share of
+    DUMP_BUDGET is written whole; a larger one as <name>_head / <name>_tail
+    (the first and last rows along its time axis: axis 1, or 0 of a vector)
+    and <name>_sample (the elements at indices drawn once from
+    numpy.random.default_rng(DUMP_SEED) over the array's shape, the same for
+    every run of the same arguments)."""
+    import numpy as np
+    import torch
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET // max(1, world) // max(1, len(arrays)) // 4  # float32 elements per array
+    tag = f"_rank{rank}" if world > 1 else ""
+
+    def save(name, part):
+        np.save(os.path.join(dirname, f"{name}{tag}.npy"), part.detach().to(torch.float32).cpu().numpy())
+    for name, t in arrays.items():
+        if t.numel() <= share:
+            save(name, t)
+            continue
+        ax = 1 if t.dim() > 1 else 0
+        n = min(max(1, share // 3 // (t.numel() // t.shape[ax])), t.shape[ax] // 2)
+        save(name + "_head", t.narrow(ax, 0, n))
+        save(name + "_tail", t.narrow(ax, t.shape[ax] - n, n))
+        flat = np.random.default_rng(DUMP_SEED).integers(0, t.numel(), share // 3)
+        idx = tuple(torch.from_numpy(i).to(t.device) for i in np.unravel_index(flat, tuple(t.shape)))
+        save(name + "_sample", t[idx])
+
+
 def bench_ir(args, dev, world, rank):
     """dsp_ir_analysis = compute_IR (plugin.cpp:17-58:
     impulse, IR_test callback over 2048 samples, 2 channels) + the Hamming
@@ -372,12 +424,15 @@ def bench_ir(args, dev, world, rank):
         d.ir_analysis(plugin, C_out=C_out, sr=float(SR), ir_len=ir_len, device=dev)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    got = None
     for _ in range(args.steps):
-        d.ir_analysis(plugin, C_out=C_out, sr=float(SR), ir_len=ir_len, device=dev)
+        got = d.ir_analysis(plugin, C_out=C_out, sr=float(SR), ir_len=ir_len, device=dev)
     torch.cuda.synchronize()
     step_s = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs and got is not None:
+        dump_outputs(args.dump_outputs, {"ir": got[0], "mag": got[1]}, world, rank)
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         import oracle as o
         plug = o.restated_plugin("IR_test")
@@ -563,6 +618,7 @@ def main():
     lib0 = d.lib()
     alg_bytes = None  # set where the library's own launch timing does not apply
     alg_flops = None  # FLOP-bound workloads (fir1024)
+    wout = epay = None  # the WAV workloads' outputs (--dump-outputs)
     alg_desc = ("fused: C*F*(4H + 4K) B (render write + |X| write; IR_test reads no input); "
                 "memory: C*F*(4H + 4K) B (each sample read once + |X| write)")
     plug_name = plugin.name
@@ -798,18 +854,26 @@ def main():
     lib.dsp_kernel_timing(C.byref(k_ms), C.byref(k_n), C.byref(k_bytes))
     ev_ms = ev0.elapsed_time(ev1)
 
+    # --dump-outputs: what the last timed step left in the caller's buffers,
+    # before any later pass (--full) writes them again
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"out": out, "mag": None if mag is None else mag[..., :K_BINS],
+                                         "wav_planar": wout, "wav_payload": epay}, world, rank)
+
     # the per-step distribution (median, p10 / p90), from a
     # separate pass with an event after every step -- those events cost a few
-    # us per step, so they stay out of the timed region above
-    nd = min(args.steps, 50)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(nd + 1)]
-    evs[0].record(stream)
-    for i in range(nd):
-        step()
-        evs[i + 1].record(stream)
-    torch.cuda.synchronize()
-    per_step = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(nd))
-    pct = lambda q: per_step[min(len(per_step) - 1, int(q * (len(per_step) - 1) + 0.5))]
+    # us per step, so they stay out of the timed region above (--full)
+    nd = min(args.steps, 50) if args.full else 0
+    pct = None
+    if nd:
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(nd + 1)]
+        evs[0].record(stream)
+        for i in range(nd):
+            step()
+            evs[i + 1].record(stream)
+        torch.cuda.synchronize()
+        per_step = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(nd))
+        pct = lambda q: per_step[min(len(per_step) - 1, int(q * (len(per_step) - 1) + 0.5))]
 
     step_s = max(wall, ev_ms / 1e3) / args.steps
     t = torch.tensor([step_s], dtype=torch.float64, device="cpu" if rehearsal else dev)
@@ -845,7 +909,7 @@ def main():
     # headline (region events, --warmup untimed then --steps); never `value`
     companion = None
     mdir = os.environ.get("DSPB_MODULES_DIR", os.path.join(REPO, "dsp-bench_amd", "modules"))
-    if (wl == "headline" and world == 1 and not args.no_companion and
+    if (args.full and wl == "headline" and world == 1 and not args.no_companion and
             os.path.exists(os.path.join(mdir, "mod_gain_test.co"))):
         try:
             companion = measure_companion(d, lib, args, x, out, mag, CH, B, sr, L, LD, soff, stream)
@@ -857,7 +921,7 @@ def main():
     # of the render and the spectra into pinned host rows
     # (dsp_render_stft_wav); never `value`
     e2e = None
-    if wl == "headline" and world == 1 and not args.no_e2e:
+    if args.full and wl == "headline" and world == 1 and not args.no_e2e:
         from dspbench import wav as dwav
         frames = L_in
         pay = torch.randint(-32768, 32768, (CH * frames,), dtype=torch.int16).view(torch.uint8).pin_memory()
@@ -890,7 +954,9 @@ def main():
     state_segments = gmod.state_spec() if wl in ("biquad_src", "sine_src", "envelope_src") else None
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and wl == "headline":
+    if not args.full:  # the CPU baselines take runs of their own
+        pass
+    elif rank == 0 and world == 1 and not args.no_cpu_baseline and wl == "headline":
         cpu = cpu_baseline(args.cpu_seconds)
     elif rank == 0 and world == 1 and not args.no_cpu_baseline and wl == "generic" and args.plugin != "IR_test":
         cpu = cpu_baseline_generic(min(args.cpu_seconds, 5.0), args.plugin or "gain_test")
@@ -948,9 +1014,10 @@ def main():
                 "first_call_ms": round(first_call_ms, 4),
                 "end_to_end": e2e,
                 "input_reading_companion": companion,
-                "settled_step_ms_p50": round(pct(0.5), 4),
-                "step_ms_p10_p50_p90": [round(pct(0.1), 4), round(pct(0.5), 4), round(pct(0.9), 4)],
-                "step_ms_distribution": f"{nd} further steps, one event after each (outside the timed region)",
+                "settled_step_ms_p50": round(pct(0.5), 4) if pct else None,
+                "step_ms_p10_p50_p90": [round(pct(0.1), 4), round(pct(0.5), 4), round(pct(0.9), 4)] if pct else None,
+                "step_ms_distribution": (f"{nd} further steps, one event after each (outside the timed region)"
+                                         if pct else None),
             },
             "roofline": ({
                 "bound": "fp32-vector",

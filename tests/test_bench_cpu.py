@@ -49,6 +49,45 @@ def test_headline_plugin_defaults_to_the_source(bench, monkeypatch):
     assert "IR_test.cpp" in name and "compiled unchanged" in name and "table" in name
 
 
+def test_plain_run_is_the_default_and_full_is_an_option(bench, monkeypatch):
+    # the passes beside the timed steps (distribution, companion, end to end, CPU baseline) need --full
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_whole_and_sampled(bench, monkeypatch, tmp_path):
+    """A small array is written whole; a large one as head, tail and a seeded
+    sample, within the budget, float32, and the same from call to call."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 2 * 4 * 3000)  # 3000 floats per array
+    small = torch.arange(2 * 500, dtype=torch.float32).reshape(2, 500)
+    big = torch.arange(2 * 50 * 41, dtype=torch.float64).reshape(2, 50, 41)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), {"out": small, "mag": big, "none": None})
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["mag_head.npy", "mag_sample.npy", "mag_tail.npy", "out.npy"]
+    got = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 2 * 4 * 3000
+    assert np.array_equal(got["out.npy"], small.numpy())
+    n = got["mag_head.npy"].shape[1]
+    assert n == 1000 // (2 * 41) and got["mag_head.npy"].shape == (2, n, 41)
+    assert np.array_equal(got["mag_head.npy"], big[:, :n].numpy().astype(np.float32))
+    assert np.array_equal(got["mag_tail.npy"], big[:, 50 - n:].numpy().astype(np.float32))
+    flat = np.random.default_rng(bench.DUMP_SEED).integers(0, big.numel(), 1000)
+    assert np.array_equal(got["mag_sample.npy"], big.reshape(-1).numpy()[flat].astype(np.float32))
+    for nme in names:
+        assert np.array_equal(np.load(tmp_path / "b" / nme), got[nme])
+    # at N > 1 every rank writes its own files, within its share
+    bench.dump_outputs(str(tmp_path / "c"), {"out": small}, world=2, rank=1)
+    assert [p.name for p in (tmp_path / "c").iterdir()] == ["out_rank1.npy"]
+
+
 def test_gpus_flag_launches_or_checks_the_world(bench):
     """--gpus N: unlaunched N > 1 starts N ranks (torch.distributed.run as a
     child, rendezvous on 127.0.0.1); under a launcher WORLD_SIZE must equal

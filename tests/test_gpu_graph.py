@@ -111,32 +111,46 @@ def test_capture_on_a_cold_stream_is_refused_cleanly(torch_cuda):
     assert "eager call" in msg or "capture" in msg
 
 
+# a one-gain plugin of this test's own (block class GAIN): the test needs no
+# module built from sources outside the repository
+PLAIN_GAIN_SRC = r'''
+#include "plugin_header.h"
+struct Parameters { FLOAT_PARAM(0.0f, 2.0f) level; };
+struct State {};
+Parameters default_parameters() { Parameters p = {0.3f}; return p; }
+State initialize_state(const Parameters &p, const unsigned C, const float sr, void *ctx) { State s; return s; }
+void audio_callback(const Parameters &p, State &st, float **out, const u32 C, const u32 B, const real32 sr) {
+    for (u32 c = 0; c < C; ++c)
+        for (u32 s = 0; s < B; ++s) out[c][s] *= p.level;
+}
+'''
+
+
 def test_generic_plugin_capture_is_refused(torch_cuda):
     """A GENERIC plugin run by its callback has its Parameters go up through a
     host-staged copy, which a graph replay would not repeat: capturing its
     render is refused with a clear error, and the eager call still works
-    afterwards.  The same plugin run as its block class (here gain_test.cpp:
-    the gain map, known from an eager call) captures and replays bit for bit."""
-    import os
+    afterwards.  The same plugin run as its block class (here PLAIN_GAIN_SRC,
+    compiled by the test: the gain map, known from an eager call) captures and
+    replays bit for bit."""
     torch = torch_cuda
-    mods = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dsp-bench_amd", "modules")
-    with open(os.path.join(mods, "mod_gain_test.co"), "rb") as f:
-        mod = d.module.Module(f.read())
+    mod = d.module.Module(d.module.compile_source(PLAIN_GAIN_SRC, "plain_gain.cpp"))
     params = mod.default_parameters()
     mod.initialize_state(params, 2, 48000.0)
-    p = mod.plugin(params, "gain_test", specialize=False)
+    p = mod.plugin(params, "plain_gain", specialize=False)
     x = torch.rand((2, 4096), device="cuda")
     want = d.render_offline(x, 2, 512, 48000.0, p).clone()
     torch.cuda.synchronize()
     msg = _refused_capture(torch, lambda: d.render_offline(x, 2, 512, 48000.0, p))
     assert "captured" in msg, msg
     assert torch.equal(d.render_offline(x, 2, 512, 48000.0, p), want)
-    ps = mod.plugin(params, "gain_test")
+    ps = mod.plugin(params, "plain_gain")
     out = torch.empty((2, 4096), device="cuda")
 
     def fn(xx):
         return (d.render_offline(xx, 2, 512, 48000.0, ps, out=out),)
     _eager_and_graph(torch, fn, x)
+    assert mod.block_class(params, 2, 512, 48000.0)[0] == "gain", mod.facts
 
 
 def test_first_use_table_under_capture_is_refused(torch_cuda):

@@ -5,7 +5,7 @@
 Prints every launch (index, start offset from the first launch, duration, gap
 to the previous launch), then the averages over the warmup launches, the
 timed launches [warmup, warmup + timed) -- the ones bench.py's step timing
-covers -- and the rest (bench.py's per-step distribution pass).
+covers -- and the rest, if any (bench.py --full's per-step distribution pass).
 """
 import csv
 import sys

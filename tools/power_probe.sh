@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 out=gpurun_out/power
 mkdir -p $out
 rocm-smi --showpower --showclocks --showtemp > $out/idle.txt 2>&1
-timeout -k 10 120 python bench.py --steps ${1:-2000} --warmup 5 --no-cpu-baseline > $out/bench.log 2>&1 &
+timeout -k 10 120 python bench.py --full --steps ${1:-2000} --warmup 5 --no-cpu-baseline > $out/bench.log 2>&1 &
 pid=$!
 for i in $(seq 1 12); do
     sleep 0.5

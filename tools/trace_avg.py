@@ -1,7 +1,7 @@
 """Average kernel duration over the timed launches of a rocprofv3 kernel trace.
 
-bench.py times --steps launches after --warmup ones (then runs up to 50 more
-for the per-step distribution); rocprofv3 --stats averages all of them, so the
+bench.py times --steps launches after --warmup ones (with --full it then runs
+up to 50 more for the per-step distribution); rocprofv3 --stats averages all of them, so the
 two agree only over the same launches:
 
     python tools/trace_avg.py <run_kernel_trace.csv> <kernel substring> [timed_n [skip_n]]
