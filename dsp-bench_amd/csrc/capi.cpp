@@ -329,6 +329,10 @@ static int ensure_ramp_table(const SampleMap &m, hipStream_t s) {
     return launch_ramp_table(const_cast<float *>(m.table), m.B, (float)m.rg0, (float)m.rs, s);
 }
 
+// DSP_DEBUG_FRAME_RUN: frames per wave of the fused IR_test launch's frame
+// reuse (0: the launch's own choice, stft8192_pk_frame_run)
+static std::atomic<uint32_t> g_frame_run{0};
+
 static int launch_stft(const Stft8kArgs &A, uint32_t C, bool fused, hipStream_t s) {
     if (fused && !(A.map.closed && stft8192_pk_per_path(A, fused))) {
         const int st = ensure_ramp_table(A.map, s);
@@ -885,6 +889,9 @@ static int verify_class(const SampleMap &orig, const float *const *in, uint32_t 
 static void set_result(const dsp_exec *ex, uint32_t bits) {
     if (ex && ex->result) *ex->result = bits;
 }
+static void or_result(const dsp_exec *ex, uint32_t bits) {
+    if (ex && ex->result) *ex->result |= bits;
+}
 
 // ---------------------------------------------------------------------------
 // host-buffer staging (DSP_EXEC_HOST_BUFFERS)
@@ -1215,12 +1222,21 @@ int dsp_device_count(void) {
 }
 
 int dsp_debug_set(int what, uint64_t value) {
+    if (what == DSP_DEBUG_FRAME_RUN) {
+        if (value > 0xffffu) return invalid("dsp_debug_set: frame run %llu > 65535", (unsigned long long)value);
+        g_frame_run.store((uint32_t)value);
+        return DSP_OK;
+    }
     if (what != DSP_DEBUG_BIQUAD_SPIN_LIMIT) return invalid("dsp_debug_set: unknown hook %d", what);
     g_iir_spin_limit.store(value > 0xffffffffull ? kIirSpinLimit : (uint32_t)value);
     return DSP_OK;
 }
 
 int dsp_debug_get(int what, uint64_t *value) {
+    if (what == DSP_DEBUG_FRAME_RUN && value) {
+        *value = g_frame_run.load();
+        return DSP_OK;
+    }
     if (what != DSP_DEBUG_BIQUAD_REPAIRS || !value) return invalid("dsp_debug_get: unknown hook %d", what);
     int dev = 0;
     if (int st = current_device(&dev)) return st;
@@ -1509,7 +1525,7 @@ int dsp_render_stft(const float *const *in, uint32_t in_channels, uint64_t L,
         const float *win = nullptr;
         if ((st = get_tw(g.dev, s, &tw))) return st;
         if ((st = get_window(g.dev, s, window, N, N, &win, window_prescale(N)))) return st;
-        bool tail_in_kernel = false;
+        bool tail_in_kernel = false, reused = false;
         for (uint32_t c0 = 0; c0 < C; c0 += kMaxChannels) {
             const uint32_t cn = (C - c0) < (uint32_t)kMaxChannels ? (C - c0) : kMaxChannels;
             Stft8kArgs A{};
@@ -1537,6 +1553,14 @@ int dsp_render_stft(const float *const *in, uint32_t in_channels, uint64_t L,
             A.goff = goff;
             // the PER kernel also renders the tail no frame owns
             if (stft8192_pk_per_path(A, true)) A.tail_end = Lr, tail_in_kernel = true;
+            // frame reuse (H % B == 0 on that path: one spectrum serves a run of
+            // frames) unless the caller asks for every frame's own FFT; a call
+            // that verifies a GENERIC plugin's class takes no shortcut that
+            // rests on the class either
+            const bool every_frame = ex && ((ex->flags & DSP_EXEC_EVERY_FRAME) ||
+                                            (orig.kind == MapKind::Generic && (ex->flags & DSP_EXEC_VERIFY_CLASS)));
+            A.run = every_frame ? 1u : stft8192_pk_frame_run(A, true, cn, g_frame_run.load());
+            if (A.run > 1) reused = true;
             TimedLaunch tl{};
             if ((st = timing_begin(s, &tl))) return st;
             if ((st = launch_stft(A, cn, true, s))) return st;
@@ -1548,6 +1572,7 @@ int dsp_render_stft(const float *const *in, uint32_t in_channels, uint64_t L,
             if (A.tail_end) bytes += (uint64_t)cn * (A.tail_end - F * (uint64_t)H) * 4;
             if ((st = timing_end(s, &tl, bytes))) return st;
         }
+        if (reused) or_result(ex, DSP_RESULT_FRAME_REUSE);
         // the render tail no frame owns: [F*H, Lr)
         if (!tail_in_kernel) {
             st = render_device(din.data(), in_channels, L, dout.data(), C, B, map, F * (uint64_t)H, goff, s);

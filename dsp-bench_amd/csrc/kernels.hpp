@@ -40,6 +40,12 @@ struct Stft8kArgs {
     const float4 *wbase; // computed-window variants: (cos, sin) of theta (2 lane), theta (2 lane + 1)
     float wa, wb;        // window w = wa - wb cos(theta n), pre-scaled
     uint64_t tail_end;   // > F H: waves F .. render [F H, tail_end) too (stft_pk PER path), else 0
+    // stft_pk PER path, frame reuse (H % B == 0: every frame of the call has the
+    // same samples): a wave owns `run` consecutive frames of a channel, computes
+    // the spectrum once and stores it `run` times.  0 / 1: one frame per wave.
+    // The caller sets run (stft8192_pk_frame_run); the launch sets run_waves.
+    uint32_t run;
+    uint64_t run_waves;  // ceil(F / run): the waves past them render the tail
 };
 
 struct GenericFftArgs {
@@ -146,6 +152,11 @@ int launch_wav_decode(const uint8_t *payload, uint32_t C, uint16_t bits, bool is
 int launch_wav_encode(uint8_t *payload, uint32_t C, uint16_t bits, bool is_float, uint64_t frames,
                       const ChanOut &in, hipStream_t s);
 bool stft8192_pk_per_path(const Stft8kArgs &A, bool fused);
+// frames per wave of the PER path's frame reuse for a launch of C channels
+// (Stft8kArgs::run): 1 when the frames differ (H % B != 0), the call is not on
+// the PER path or it is too short to fill the device; `forced` > 0 (test hook)
+// replaces the default wherever reuse is valid
+uint32_t stft8192_pk_frame_run(const Stft8kArgs &A, bool fused, uint32_t C, uint32_t forced);
 int stft_pk_ab_options();  // A/B option bits of this thread: 0 unless the tools build (stft_pk_ab.hip) set them
 int launch_stft8192_pk(const Stft8kArgs &A, uint32_t C, bool fused, int opt, hipStream_t s);
 int launch_fft_generic(const GenericFftArgs &A, uint64_t transforms, uint32_t C, hipStream_t s);

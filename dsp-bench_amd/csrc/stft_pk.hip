@@ -40,10 +40,36 @@ bool stft8192_pk_per_path(const Stft8kArgs &A, bool fused) {
     return fused && A.map.kind == MapKind::Ramp && pow2 && winc && A.map.B <= 2048u;
 }
 
+// Frame reuse.  On the PER path a frame is table[(goff + f H + n) & (B - 1)]:
+// with H % B == 0 it does not depend on f, so every frame of the call has the
+// same samples and the same spectrum, and a wave can compute it once for a run
+// of frames and only repeat the stores.  The default run is kPkRunMax frames,
+// and never more than the static split of the call over the wave slots of the
+// device (kPkWaveSlots / C per channel), so that a call too short to fill them
+// keeps one frame per wave (run 1), which finishes sooner than fewer, longer
+// waves would.  kPkRunMax = 4 is measured (profiles/r07_frame_run_ab.txt):
+// runs of 4 to 42 are equally fast on a machine that lets the launch run at
+// full clock, and on one that does not the time grows with the run; 4 is the
+// longest that is not behind one FFT per frame there.
+constexpr uint32_t kPkWaveSlots = 256u * 4u * 2u;  // MI355X: 256 CUs x 4 SIMDs x 2 waves (amdgpu_waves_per_eu 2)
+constexpr uint32_t kPkRunMax = 4;
+uint32_t stft8192_pk_frame_run(const Stft8kArgs &A, bool fused, uint32_t C, uint32_t forced) {
+    if (!stft8192_pk_per_path(A, fused) || A.map.B == 0 || A.H % A.map.B != 0 || A.F == 0 || C == 0) return 1;
+    if (forced) return forced;
+    const uint64_t slots = kPkWaveSlots / C ? kPkWaveSlots / C : 1;
+    const uint64_t run = (A.F + slots - 1) / slots;
+    return (uint32_t)(run < kPkRunMax ? run : kPkRunMax);
+}
+
 // A.win2: the window pre-scaled by 0.5 / sqrt(8192); the computed window
 // (A.wbase, A.wa, A.wb) serves the full-frame 4097-bin shapes.
-int launch_stft8192_pk(const Stft8kArgs &A, uint32_t C, bool fused, int opt, hipStream_t stream) {
-    if (A.F == 0 || C == 0) return DSP_OK;
+int launch_stft8192_pk(const Stft8kArgs &A_, uint32_t C, bool fused, int opt, hipStream_t stream) {
+    if (A_.F == 0 || C == 0) return DSP_OK;
+    Stft8kArgs A = A_;
+    if (A.run == 0) A.run = 1;
+    // a run of frames is one spectrum: only where stft8192_pk_frame_run allows it
+    if (A.run > 1 && stft8192_pk_frame_run(A, fused, C, A.run) != A.run) return DSP_ERR_INVALID;
+    A.run_waves = (A.F + A.run - 1) / A.run;
     // PER path: extra waves for the render tail [F H, tail_end)
     const uint64_t tail = A.tail_end > A.F * A.H ? (A.tail_end - A.F * A.H + A.H - 1) / A.H : 0;
     if (tail && !stft8192_pk_per_path(A, fused)) return DSP_ERR_INVALID;
@@ -58,12 +84,23 @@ int launch_stft8192_pk(const Stft8kArgs &A, uint32_t C, bool fused, int opt, hip
         const uint32_t per = A.map.B <= 128u ? 1u : A.map.B / 128u;
         if (per == 4 && opt) {  // A/B at the headline shape (the tools build only: stft_pk_ab.hip)
             int st = DSP_OK;
-            if (stft_pk_ab_dispatch(A, C, fused, opt, grid, stream, &st)) return st;
+            Stft8kArgs A1 = A;  // the variants size their grids for one frame per wave
+            A1.run = 1;
+            A1.run_waves = A.F;
+            if (stft_pk_ab_dispatch(A1, C, fused, opt, grid, stream, &st)) return st;
         }
-#define DSPB_PK_PER(p) \
-    hipLaunchKernelGGL((stft8192_pk_kernel<kSrcRender, kKHalf, MapKind::Ramp, true, true, p, kPkPerOpt>), grid_per, \
-                       dim3(64 * kPkPerWpb), 0, stream, A)
-        const uint64_t groups_per = (A.F + tail + kPkPerWpb - 1) / kPkPerWpb;
+        // (run 1: the instantiation without the reuse path, the per-frame kernel as it was)
+#define DSPB_PK_PER(p)                                                                                                \
+    do {                                                                                                              \
+        if (A.run > 1)                                                                                                \
+            hipLaunchKernelGGL((stft8192_pk_kernel<kSrcRender, kKHalf, MapKind::Ramp, true, true, p, kPkPerOpt>),    \
+                               grid_per, dim3(64 * kPkPerWpb), 0, stream, A);                                         \
+        else                                                                                                          \
+            hipLaunchKernelGGL(                                                                                       \
+                (stft8192_pk_kernel<kSrcRender, kKHalf, MapKind::Ramp, true, true, p, kPkPerOpt | kPkNoReuse>),       \
+                grid_per, dim3(64 * kPkPerWpb), 0, stream, A);                                                        \
+    } while (0)
+        const uint64_t groups_per = (A.run_waves + tail + kPkPerWpb - 1) / kPkPerWpb;
         if (groups_per > 0x7fffffffull) return DSP_ERR_INVALID;
         const dim3 grid_per((uint32_t)groups_per, C);
         switch (per) {

@@ -43,7 +43,11 @@ namespace dspb {
 enum { kPkNoBarDft = 1, kPkNoBarTw = 2, kPkNoBarSplit = 4, kPkRenderCached = 8, kPkNtMag = 16, kPkMagLds = 32,
        kPkOldSplit = 64, kPkAbNoRender = 128, kPkAbNoMag = 256, kPkMagStage = 512, kPkOcc3 = 1024,
        kPkMemAos = 2048, kPkNoRemap = 4096, kPkAbNoXpose = 8192, kPkMemPf = 16384, kPkW1 = 65536,
-       kPkMemHop = 131072 };
+       kPkMemHop = 131072, kPkNoReuse = 262144 };
+// 262144 = the PER kernel without the frame-reuse path: the one-frame-per-wave
+// launches (H % B != 0, DSP_EXEC_EVERY_FRAME, short calls) run it, so that their
+// code is what it was before the reuse path existed (with the path compiled in
+// and run = 1 the per-frame case was 2.4% slower, profiles/r07_frame_run_ab.txt)
 // 65536 = one wave per workgroup (64 threads, one 64 x 65 tile): a slot frees as its frame ends
 // 131072 = memory frames on stft8192_mem_hop_kernel (a workgroup's 5 hops staged once in LDS)
 // 16384 = memory frames on stft8192_mem_pf_kernel (persistent, LDS hop prefetch)
@@ -107,10 +111,17 @@ __device__ __forceinline__ void put_bin(float *mrow, uint32_t K, uint32_t k, flo
 // and bin 2048 with itself).  Bins 1024 / 3072 (lane 0, Y2[16]) are left
 // over and done at the end.  Bins per iteration: l + 64 q, 2048 + l + 64 q,
 // 4096 - l - 64 q, 2048 - l - 64 q.
-template <int KM, bool BAR, bool NOSTORE = false, bool STAGE = false, bool STAGE_NT = false>
+//
+// KEEP (frame reuse): no global store; the lane's magnitudes are parked in the
+// wave's LDS tile (free after the transpose), M[64 j + lane] for j < 64 and
+// lane 0's bins 1024 / 3072 at M[4096], M[4097], in the order store_row_y2
+// stores them.  (Kept in registers beside Y2 they spill: 256 VGPRs + scratch.)
+constexpr int kPkRowRegs = 66;
+template <int KM, bool BAR, bool NOSTORE = false, bool STAGE = false, bool STAGE_NT = false, bool KEEP = false>
 __device__ __forceinline__ void split_y2(const cx2 (&Y2)[32], float *mrow, uint32_t K, const v2f *tw,
-                                         uint32_t lane, float *lds) {
+                                         uint32_t lane, float *lds, float *M = nullptr) {
     static_assert(!STAGE || KM == kKHalf, "staged rows: 4097 bins");
+    static_assert(!KEEP || (KM == kKHalf && !NOSTORE && !STAGE), "kept rows: 4097 bins, the dword row stores");
     float acc = 0.f;  // NOSTORE: keeps the magnitudes live
     // STAGE: bin k goes to lds[k + a], a = the row's dword phase mod 4, so
     // LDS float4 j is the 16-byte-aligned global piece at bins [4j - a, 4j - a + 4)
@@ -147,7 +158,12 @@ __device__ __forceinline__ void split_y2(const cx2 (&Y2)[32], float *mrow, uint3
         const v2f q1 = X1.r * X1.r + X1.i * X1.i;
         const v2f q2 = X2.r * X2.r + X2.i * X2.i;
         const uint32_t k = lane + 64u * (uint32_t)q;
-        if constexpr (NOSTORE) {
+        if constexpr (KEEP) {
+            (M + lane)[64 * (4 * q)] = __builtin_amdgcn_sqrtf(q1.x);
+            (M + lane)[64 * (4 * q + 1)] = __builtin_amdgcn_sqrtf(q1.y);
+            (M + lane)[64 * (4 * q + 2)] = __builtin_amdgcn_sqrtf(q2.x);
+            (M + lane)[64 * (4 * q + 3)] = __builtin_amdgcn_sqrtf(q2.y);
+        } else if constexpr (NOSTORE) {
             acc += __builtin_amdgcn_sqrtf(q1.x) + __builtin_amdgcn_sqrtf(q1.y) + __builtin_amdgcn_sqrtf(q2.x) +
                    __builtin_amdgcn_sqrtf(q2.y);
         } else if constexpr (STAGE) {
@@ -179,7 +195,10 @@ __device__ __forceinline__ void split_y2(const cx2 (&Y2)[32], float *mrow, uint3
         const cx X1 = E + T, X2 = E - T;
         const float m1 = __builtin_amdgcn_sqrtf(__builtin_fmaf(X1.r, X1.r, X1.i * X1.i));
         const float m2 = __builtin_amdgcn_sqrtf(__builtin_fmaf(X2.r, X2.r, X2.i * X2.i));
-        if constexpr (STAGE) {
+        if constexpr (KEEP) {
+            M[4096] = m1;
+            M[4097] = m2;
+        } else if constexpr (STAGE) {
             sl[1024] = m1;
             sl[3072] = m2;
         } else {
@@ -208,6 +227,23 @@ __device__ __forceinline__ void split_y2(const cx2 (&Y2)[32], float *mrow, uint3
     }
 }
 
+// The row stores of split_y2<kKHalf> (same instructions, same addresses) from
+// the magnitudes split_y2<.., KEEP> left in M.
+template <bool NT>
+__device__ __forceinline__ void store_row_y2(const float (&M)[kPkRowRegs], float *mrow, uint32_t lane) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        st<NT>(&(mrow + lane)[64 * q], M[4 * q]);
+        st<NT>(&(mrow + 2048u + lane)[64 * q], M[4 * q + 1]);
+        st<NT>(&(mrow + 4096u - lane)[-64 * q], M[4 * q + 2]);
+        st<NT>(&(mrow + 2048u - lane)[-64 * q], M[4 * q + 3]);
+    }
+    if (lane == 0) {
+        mrow[1024] = M[64];
+        mrow[3072] = M[65];
+    }
+}
+
 // PER (Ramp, pow2 B <= 4096): the frame's sample pairs repeat every PER
 // values of b (PER = max(1, B / 128)), so only v[0 .. PER) are fetched from
 // the block table -- 4 gathers at B = 512 -- and v[b] = v[b mod PER] is a
@@ -219,6 +255,50 @@ constexpr uint32_t pk_waves_per_block() { return (OPT & kPkW1) ? 1u : 4u; }
 constexpr uint32_t kPkWpb = pk_waves_per_block<kPkDefaultOpt>();
 constexpr uint32_t kPkPerWpb = pk_waves_per_block<kPkPerOpt>();
 
+// PER frames: the distinct sample pairs of the frame whose first sample is at
+// table position p0 - 2 lane, X[jj] = ((x_e(2jj), x_e(2jj+1)), (x_o(2jj), x_o(2jj+1)))
+template <int PER>
+__device__ __forceinline__ void per_gather(const Stft8kArgs &A, uint32_t p0, cx2 (&X)[PER >= 2 ? PER / 2 : 1]) {
+    constexpr int NJ = PER >= 2 ? PER / 2 : 1;
+    const float *T = A.map.table;
+    if (A.map.closed) {  // table values in closed form (common.hpp ramp_value)
+#pragma unroll
+        for (int jj = 0; jj < NJ; ++jj) {
+            const uint32_t q0 = (p0 + 256u * jj) & A.map.b_mask;
+            const uint32_t q1 = (p0 + 256u * jj + (PER >= 2 ? 128u : 0u)) & A.map.b_mask;
+            X[jj] = cx2{v2f{ramp_value(A.map, q0), ramp_value(A.map, q1)},
+                        v2f{ramp_value(A.map, q0 + 1), ramp_value(A.map, q1 + 1)}};
+        }
+    } else {
+#pragma unroll
+        for (int jj = 0; jj < NJ; ++jj) {
+            const uint32_t q0 = (p0 + 256u * jj) & A.map.b_mask;
+            const uint32_t q1 = (p0 + 256u * jj + (PER >= 2 ? 128u : 0u)) & A.map.b_mask;
+            X[jj] = cx2{v2f{T[q0], T[q1]}, v2f{T[q0 + 1], T[q1 + 1]}};
+        }
+    }
+}
+
+// the render output of one hop at o: sample pairs of column b repeat with period PER
+template <int PER, bool NT>
+__device__ __forceinline__ void per_render_hop(const Stft8kArgs &A, float *o, uint32_t lane,
+                                               const cx2 (&X)[PER >= 2 ? PER / 2 : 1]) {
+    constexpr int NS = PER >= 2 ? PER : 1;
+    v2f st[NS];
+#pragma unroll
+    for (int b = 0; b < NS; ++b) st[b] = v2f{X[b / 2].r[b & 1], X[b / 2].i[b & 1]};
+    if (A.H == 4096u) {  // the headline hop: 32 columns, no per-store branch
+#pragma unroll
+        for (int b = 0; b < 32; ++b)
+            dspb::st<NT>(reinterpret_cast<v2f *>(o + 128u * (uint32_t)b) + lane, st[b % NS]);
+    } else {
+#pragma unroll
+        for (int b = 0; b < 64; ++b)
+            if (128u * (uint32_t)b < A.H)
+                dspb::st<NT>(reinterpret_cast<v2f *>(o + 128u * (uint32_t)b) + lane, st[b % NS]);
+    }
+}
+
 template <int SRC, int KM, MapKind MK, bool POW2, bool WINC, int PER = 0, int OPT = kPkDefaultOpt, int OCC = 2>
 // (OCC waves per SIMD whatever the workgroup size: stated as waves per EU,
 // which __launch_bounds__' workgroup count does not pin for one-wave groups)
@@ -229,8 +309,27 @@ void stft8192_pk_kernel(Stft8kArgs A) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t ch = blockIdx.y;
-    const uint64_t f = (uint64_t)((OPT & kPkNoRemap) ? blockIdx.x : xcd_remap(blockIdx.x, gridDim.x)) * WPB + wave;
+    uint64_t f = (uint64_t)((OPT & kPkNoRemap) ? blockIdx.x : xcd_remap(blockIdx.x, gridDim.x)) * WPB + wave;
     constexpr bool SOA = WINC && MK == MapKind::Ramp && PER > 0 && SRC == kSrcRender;
+    // frame reuse (A.run > 1; the launch checked H % B == 0, so every frame of
+    // the call holds the same samples): wave w owns the frames [w run, w run +
+    // nrun) of its channel -- one gather, window, FFT and split, then nrun
+    // times the stores of a frame; waves run_waves .. render the tail.  The
+    // XCD remap hands each XCD consecutive waves, hence consecutive frames.
+    constexpr bool REUSE = SOA && KM == kKHalf && OCC == 2 &&
+                           !(OPT & (kPkNoReuse | kPkOldSplit | kPkMagLds | kPkMagStage | kPkAbNoRender | kPkAbNoMag | kPkAbNoXpose));
+    uint32_t nrun = 1;
+    if constexpr (REUSE) {
+        if (A.run > 1u) {
+            if (f < A.run_waves) {
+                f *= A.run;
+                const uint64_t left = A.F - f;
+                nrun = left < A.run ? (uint32_t)left : A.run;
+            } else {
+                f = A.F + (f - A.run_waves);
+            }
+        }
+    }
     // memory frames with the computed window: two dwordx2 loads per pair
     // (columns 2j, 2j+1) regrouped into even/odd halves
     constexpr bool MSOA = WINC && SRC == kSrcMemory && !(OPT & kPkMemAos);
@@ -299,43 +398,10 @@ void stft8192_pk_kernel(Stft8kArgs A) {
         constexpr int NJ = PER >= 2 ? PER / 2 : 1;
         cx2 X[NJ];
         if constexpr (SOA) {
-            const uint32_t p0 = (uint32_t)(A.goff + fs) + 2u * lane;
-            const float *T = A.map.table;
-            if (A.map.closed) {  // table values in closed form (common.hpp ramp_value)
-#pragma unroll
-                for (int jj = 0; jj < NJ; ++jj) {
-                    const uint32_t q0 = (p0 + 256u * jj) & A.map.b_mask;
-                    const uint32_t q1 = (p0 + 256u * jj + (PER >= 2 ? 128u : 0u)) & A.map.b_mask;
-                    X[jj] = cx2{v2f{ramp_value(A.map, q0), ramp_value(A.map, q1)},
-                                v2f{ramp_value(A.map, q0 + 1), ramp_value(A.map, q1 + 1)}};
-                }
-            } else {
-#pragma unroll
-                for (int jj = 0; jj < NJ; ++jj) {
-                    const uint32_t q0 = (p0 + 256u * jj) & A.map.b_mask;
-                    const uint32_t q1 = (p0 + 256u * jj + (PER >= 2 ? 128u : 0u)) & A.map.b_mask;
-                    X[jj] = cx2{v2f{T[q0], T[q1]}, v2f{T[q0 + 1], T[q1 + 1]}};
-                }
-            }
-            // the render output: sample pairs of column b repeat with period PER
-            float *o = A.out.p[ch] + fs;
-            v2f st[PER >= 2 ? PER : 1];
-#pragma unroll
-            for (int b = 0; b < (PER >= 2 ? PER : 1); ++b)
-                st[b] = v2f{X[b / 2].r[b & 1], X[b / 2].i[b & 1]};
-            constexpr bool NT = !(OPT & kPkRenderCached);
-            if (OPT & kPkAbNoRender) {
-            } else if (A.H == 4096u) {  // the headline hop: 32 columns, no per-store branch
-#pragma unroll
-                for (int b = 0; b < 32; ++b)
-                    dspb::st<NT>(reinterpret_cast<v2f *>(o + 128u * (uint32_t)b) + lane, st[b % (PER >= 2 ? PER : 1)]);
-            } else {
-#pragma unroll
-                for (int b = 0; b < 64; ++b)
-                    if (128u * (uint32_t)b < A.H)
-                        dspb::st<NT>(reinterpret_cast<v2f *>(o + 128u * (uint32_t)b) + lane,
-                                     st[b % (PER >= 2 ? PER : 1)]);
-            }
+            per_gather<PER>(A, (uint32_t)(A.goff + fs) + 2u * lane, X);
+            // (a reused frame's hops are stored after the FFT, with its rows)
+            if (!(OPT & kPkAbNoRender) && nrun == 1u)
+                per_render_hop<PER, !(OPT & kPkRenderCached)>(A, A.out.p[ch] + fs, lane, X);
         }
         // w(n) = wa - wb cos(theta n) = wa - u C_b + v S_b per parity, with
         // u = wb cos(theta n0), v = wb sin(theta n0) of the lane's base angle
@@ -477,6 +543,29 @@ void stft8192_pk_kernel(Stft8kArgs A) {
         if constexpr (OCC >= 3) fft4096_pk_y2_lo<!(OPT & kPkNoBarDft)>(P, lds, A.tw, lane, Y2);
         else fft4096_pk_y2<!(OPT & kPkNoBarDft), !(OPT & kPkNoBarTw), (OPT & kPkAbNoXpose) != 0, NoHook, W4>(
             P, lds, tlo, thp, lane, Y2);
+        if constexpr (REUSE) {
+            if (nrun > 1u) {
+                // the spectrum once into registers, the samples gathered again
+                // (not held across the FFT), then each frame's stores: what
+                // nrun one-frame waves would have stored, from the same values
+                static_assert(64 * 65 >= 4098, "the kept row fits the wave's LDS tile");
+                split_y2<KM, !(OPT & kPkNoBarSplit), false, false, false, true>(Y2, nullptr, A.K, A.tw, lane, lds, lds);
+                float M[kPkRowRegs];  // each lane reads back what it parked (lane 0: and its two extra bins)
+#pragma unroll
+                for (int j = 0; j < 64; ++j) M[j] = (lds + lane)[64 * j];
+                M[64] = lds[4096];
+                M[65] = lds[4097];
+                cx2 X[PER >= 2 ? PER / 2 : 1];
+                per_gather<PER>(A, (uint32_t)(A.goff + fs) + 2u * lane, X);
+                float *o = A.out.p[ch] + fs;
+                float *mrow = A.mag.p[ch] + f * A.ld;
+                for (uint32_t r = 0; r < nrun; ++r, o += A.H, mrow += A.ld) {
+                    per_render_hop<PER, !(OPT & kPkRenderCached)>(A, o, lane, X);
+                    store_row_y2<(OPT & kPkNtMag) != 0>(M, mrow, lane);
+                }
+                return;
+            }
+        }
         split_y2<KM, !(OPT & kPkNoBarSplit), (OPT & kPkAbNoMag) != 0, KM == kKHalf && (OPT & kPkMagStage) != 0,
                  (OPT & kPkNtMag) != 0>(Y2, A.mag.p[ch] + f * A.ld, A.K, A.tw, lane, lds);
         return;

@@ -35,9 +35,14 @@ DSP_EXEC_FIR_DIRECT = 0x4
 DSP_EXEC_NO_SPECIALIZE = 0x8
 DSP_EXEC_VERIFY_CLASS = 0x10
 DSP_EXEC_SERIAL_STATE = 0x20
+DSP_EXEC_EVERY_FRAME = 0x40
+DSP_EXEC_METHOD_FLAGS = (DSP_EXEC_FIR_DIRECT | DSP_EXEC_NO_SPECIALIZE | DSP_EXEC_VERIFY_CLASS |
+                         DSP_EXEC_SERIAL_STATE | DSP_EXEC_EVERY_FRAME)
 DSP_RESULT_CLASS = 0x1
 DSP_RESULT_VERIFIED = 0x2
 DSP_RESULT_RERENDERED = 0x4
+DSP_RESULT_FRAME_REUSE = 0x8
+DSP_DEBUG_FRAME_RUN = 3  # dsp_debug_set / _get: frames per wave of the frame reuse (test hook)
 DSP_BLOCK_CALLBACK, DSP_BLOCK_TABLE, DSP_BLOCK_GAIN, DSP_BLOCK_GAIN_TABLE = 0, 1, 2, 3
 
 

@@ -50,8 +50,11 @@ class Plugin:
         return Plugin(L.DSP_PLUGIN_GAIN, struct.pack("<f", gain), b"", "gain_test")
 
     @staticmethod
-    def ir_test(gain: float = 0.9, step: float = 0.002) -> "Plugin":
-        return Plugin(L.DSP_PLUGIN_IR_RAMP, struct.pack("<ff", gain, step), b"", "IR_test")
+    def ir_test(gain: float = 0.9, step: float = 0.002, every_frame: bool = False) -> "Plugin":
+        """every_frame: the fused render + STFT computes every frame's FFT
+        (DSP_EXEC_EVERY_FRAME) even where all frames are the same (H % B == 0)."""
+        return Plugin(L.DSP_PLUGIN_IR_RAMP, struct.pack("<ff", gain, step), b"", "IR_test",
+                      exec_flags=L.DSP_EXEC_EVERY_FRAME if every_frame else 0)
 
     @staticmethod
     def static_gain(gain: float = 0.1) -> "Plugin":
@@ -154,8 +157,8 @@ _tls = threading.local()
 
 def last_result() -> int:
     """dsp_exec.result of this thread's last render_offline / render_stft /
-    render_loop / render_stft_host (DSP_RESULT_CLASS / _VERIFIED / _RERENDERED
-    bits; the chunked driver ORs its chunks' bits)."""
+    render_loop / render_stft_host (DSP_RESULT_CLASS / _VERIFIED / _RERENDERED /
+    _FRAME_REUSE bits; the chunked driver ORs its chunks' bits)."""
     return getattr(_tls, "result", 0)
 
 

@@ -239,20 +239,25 @@ class Module:
         return buf.raw[:self.state_size]
 
     def plugin(self, params: bytes, name: str = "generic", specialize: bool = True, verify: bool = False,
-               serial_state: bool = False):
+               serial_state: bool = False, every_frame: bool = False):
         """A GENERIC plugin over this module.  specialize=False runs the
         plugin's callback on every block (DSP_EXEC_NO_SPECIALIZE); by default
         a plugin whose block class its IR proves runs as that class
         (block_class).  verify=True checks blocks of every call against the
         callback (DSP_EXEC_VERIFY_CLASS; dspbench.api.last_result()).
         serial_state=True renders a State-writing callback as one chain
-        (DSP_EXEC_SERIAL_STATE) instead of speculative segments (state_spec)."""
+        (DSP_EXEC_SERIAL_STATE) instead of speculative segments (state_spec).
+        every_frame=True: a table class's fused render + STFT computes every
+        frame's FFT (DSP_EXEC_EVERY_FRAME; default: one spectrum per run of
+        frames when H % B == 0)."""
         from .api import Plugin
         flags = 0 if specialize else L.DSP_EXEC_NO_SPECIALIZE
         if verify:
             flags |= L.DSP_EXEC_VERIFY_CLASS
         if serial_state:
             flags |= L.DSP_EXEC_SERIAL_STATE
+        if every_frame:
+            flags |= L.DSP_EXEC_EVERY_FRAME
         return Plugin(L.DSP_PLUGIN_GENERIC, bytes(params), b"", name, self, exec_flags=flags)
 
     def state_spec(self) -> dict:

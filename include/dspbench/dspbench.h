@@ -120,16 +120,29 @@ typedef struct dsp_plugin {
                                       of blocks in order on one lane, as the reference's audio thread
                                       runs them (default: speculative segments, module.h
                                       dsp_state_spec_info -- the same bits) */
+#define DSP_EXEC_EVERY_FRAME 0x40u  /* dsp_render_stft, fused IR_test launch (DSP_PLUGIN_IR_RAMP, or a
+                                      GENERIC plugin whose block class is one table): compute every
+                                      frame's FFT.  Default: when the hop is a multiple of the block
+                                      size (H % B == 0) every frame of the call holds the same
+                                      samples, and a call long enough to fill the device computes
+                                      the spectrum once per wave and stores it for a run of frames
+                                      (DSP_RESULT_FRAME_REUSE) -- the same bits, nothing kept between
+                                      calls.  A GENERIC call with DSP_EXEC_VERIFY_CLASS computes
+                                      every frame too */
 /* the flags that choose how a call computes (not where its buffers live):
  * the chunked and sharded drivers pass them on to every chunk */
-#define DSP_EXEC_METHOD_FLAGS \
-    (DSP_EXEC_FIR_DIRECT | DSP_EXEC_NO_SPECIALIZE | DSP_EXEC_VERIFY_CLASS | DSP_EXEC_SERIAL_STATE)
+#define DSP_EXEC_METHOD_FLAGS                                                                    \
+    (DSP_EXEC_FIR_DIRECT | DSP_EXEC_NO_SPECIALIZE | DSP_EXEC_VERIFY_CLASS | DSP_EXEC_SERIAL_STATE | \
+     DSP_EXEC_EVERY_FRAME)
 
 /* dsp_exec.result bits (written when result is not NULL) */
 #define DSP_RESULT_CLASS 0x1u      /* a GENERIC plugin ran as its block class */
 #define DSP_RESULT_VERIFIED 0x2u   /* DSP_EXEC_VERIFY_CLASS: the checked blocks matched */
 #define DSP_RESULT_RERENDERED 0x4u /* DSP_EXEC_VERIFY_CLASS: a checked block differed; the call was
                                       rendered again with the callback on every block */
+#define DSP_RESULT_FRAME_REUSE 0x8u /* dsp_render_stft: the fused launch computed one spectrum per
+                                      run of frames (see DSP_EXEC_EVERY_FRAME); the chunked and
+                                      sharded drivers OR it across their chunks */
 
 typedef struct dsp_exec {
     int32_t device;         /* HIP device ordinal; -1 = current device */
@@ -159,8 +172,12 @@ int dsp_biquad_plan(const float *coef, uint32_t sections, uint32_t *window);
  *   (within the same bound).  0 gives up wherever a word is not there at the
  *   first look.
  * DSP_DEBUG_BIQUAD_REPAIRS (get): launches on the current device rendered
- *   again that way since the last get (read it after the renders finished). */
-enum { DSP_DEBUG_BIQUAD_SPIN_LIMIT = 1, DSP_DEBUG_BIQUAD_REPAIRS = 2 };
+ *   again that way since the last get (read it after the renders finished).
+ * DSP_DEBUG_FRAME_RUN (set / get): frames per wave of the frame reuse (see
+ *   DSP_EXEC_EVERY_FRAME) wherever it is valid, whatever the call's length
+ *   (1..65535; 1 = every frame; 0 restores the launch's own choice).
+ *   Process-wide: for tests and A/B runs. */
+enum { DSP_DEBUG_BIQUAD_SPIN_LIMIT = 1, DSP_DEBUG_BIQUAD_REPAIRS = 2, DSP_DEBUG_FRAME_RUN = 3 };
 int dsp_debug_set(int what, uint64_t value);
 int dsp_debug_get(int what, uint64_t *value);
 
