@@ -20,8 +20,10 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -42,96 +44,68 @@ constexpr uint64_t kStagedLdsBytes = 64 * 1024;  // stateful render's LDS double
 #define DSPB_LDS_ROUND (76 * 1024)
 #define DSPB_LDS_WGS 2
 #endif
-// LDS per workgroup round of the stateless LDS-blocks path (kDriver
-// dspb_lds_nb: the same formula, handed to hiprtc as DSPB_LDS_ROUND_BYTES),
-// and the persistent grid's workgroups per CU
-constexpr uint64_t kLdsRoundBytes = DSPB_LDS_ROUND;
+// LDS per workgroup round of the LDS-blocks and segment kernels (handed to
+// hiprtc as DSPB_LDS_ROUND_BYTES: the round geometry of plugin_driver_abi.h is
+// computed from it on both sides), and the persistent grid's workgroups per CU
+#define DSPB_LDS_ROUND_BYTES DSPB_LDS_ROUND
+constexpr uint64_t kLdsRoundBytes = DSPB_LDS_ROUND_BYTES;
 constexpr uint64_t kLdsWgPerCu = DSPB_LDS_WGS;
 
-// the LDS-blocks kernels of kDriver: (C, B) = 0 matches any value
-struct LdsShape {
+// the contract with the driver kernels: dspb_render_args / dspb_seg_args (a
+// State is bytes here), the round geometry, the counters' slots and the
+// kernel lists
+#include "plugin_driver_abi.h"
+// the layout of the parent revision's argument blocks, as a host program
+// printed it: code objects compiled before the structs were shared still load
+static_assert(sizeof(dspb_render_args) == 328 && sizeof(dspb_seg_args) == 448, "argument block sizes");
+static_assert(offsetof(dspb_seg_args, R) + offsetof(dspb_render_args, par) == 324, "dspb_render_args.par");
+static_assert(offsetof(dspb_seg_args, seg) == 384 && offsetof(dspb_seg_args, perturb) == 424 &&
+                  offsetof(dspb_seg_args, split) == 440,
+              "dspb_seg_args fields");
+static_assert(dspb_max_channels == (unsigned)dspb::kMaxChannels, "one channel bound");
+
+// a kernel of the driver and the shape it is compiled for: (C, B) = 0 matches
+// any value; the tables list the most specific first
+struct Shape {
     const char *name;
     uint32_t C, B;
+    const char *rerun;  // segments: the reruns' kernel (NULL: the same one)
+    bool pf;            // segments: blocks at dspb_stride_pf, and 4 | B
 };
-constexpr LdsShape kLdsShapes[7] = {{"dspb_render_lds", 0, 0},         {"dspb_render_lds_c2b512", 2, 512},
-                                    {"dspb_render_lds_c2b256", 2, 256}, {"dspb_render_lds_c2b1024", 2, 1024},
-                                    {"dspb_render_lds_c1b512", 1, 512}, {"dspb_render_lds_c1", 1, 0},
-                                    {"dspb_render_lds_c2", 2, 0}};
-// the stateful LDS path's kernels: dspb_render covers every other shape
-constexpr LdsShape kStShapes[4] = {{"dspb_render_st_c2b512", 2, 512}, {"dspb_render_st_c2b256", 2, 256},
-                                   {"dspb_render_st_c1", 1, 0}, {"dspb_render_st_c2", 2, 0}};
-// speculative segments of a stateful render (kDriver dspb_segments): pass 1 /
-// rerun kernels, most specific first, and the walk's
-// (pass 1, its reruns; pipelined: blocks at a stride of C B + 2 and 4 | B)
-struct SegShape {
-    const char *name, *rerun;
-    uint32_t C, B;
-    bool pf;
-};
-constexpr SegShape kSegShapes[5] = {{"dspb_seg_c2b512", "dspb_seg_c2b512_rerun", 2, 512, true},
-                                    {"dspb_seg_c2", "dspb_seg_c2_rerun", 2, 0, true},
-                                    {"dspb_seg_c1", "dspb_seg_c1_rerun", 1, 0, true},
-                                    {"dspb_seg_c4", "dspb_seg_c4_rerun", 4, 0, true},
-                                    {"dspb_seg", nullptr, 0, 0, false}};
-constexpr LdsShape kWalkShapes[2] = {{"dspb_seg_walk_c2b512", 2, 512}, {"dspb_seg_walk_any", 0, 0}};
-// the chain kernels of a State that never forgets (kSegDriver dspb_seg_chain;
-// B = 0: any B <= kChainMaxB, the private block sized for it)
-constexpr LdsShape kChainShapes[4] = {{"dspb_seg_chain_c2b512", 2, 512}, {"dspb_seg_chain_c2", 2, 0},
-                                      {"dspb_seg_chain_c1", 1, 0}, {"dspb_seg_chain_c4", 4, 0}};
-// the chain of a split State's block-independent words, the same shapes
-constexpr LdsShape kChainIndShapes[4] = {{"dspb_seg_chain_ind_c2b512", 2, 512}, {"dspb_seg_chain_ind_c2", 2, 0},
-                                         {"dspb_seg_chain_ind_c1", 1, 0}, {"dspb_seg_chain_ind_c4", 4, 0}};
-constexpr uint32_t kChainMaxB = 4096;
+#define DSPB_SHAPE(name, C, B) {#name, C, B, nullptr, false},
+#define DSPB_SEG_PF_roles true
+#define DSPB_SEG_PF_pf true
+#define DSPB_SEG_PF_any false
+#define DSPB_SEG_RERUN_pf(name) #name "_rerun"
+#define DSPB_SEG_RERUN_same(name) nullptr
+#define DSPB_SEG_SHAPE(name, C, B, P1, RR) {#name, C, B, DSPB_SEG_RERUN_##RR(name), DSPB_SEG_PF_##P1},
+constexpr Shape kLdsShapes[] = {DSPB_LDS_KERNELS(DSPB_SHAPE)};
+constexpr Shape kStShapes[] = {DSPB_ST_KERNELS(DSPB_SHAPE)};
+constexpr Shape kSegShapes[] = {DSPB_SEG_KERNELS(DSPB_SEG_SHAPE)};
+constexpr Shape kWalkShapes[] = {DSPB_WALK_KERNELS(DSPB_SHAPE)};
+constexpr Shape kChainShapes[] = {DSPB_CHAIN_KERNELS(DSPB_SHAPE)};
+constexpr Shape kChainIndShapes[] = {DSPB_CHAIN_IND_KERNELS(DSPB_SHAPE)};
+static_assert(std::size(kChainShapes) == std::size(kChainIndShapes), "the chains of one shape list");
+// the first kernel of a table that is loaded (ok(i)) and compiled for (C, B);
+// a shape of any B takes B <= max_b.  -1: none
+template <size_t N, class Ok>
+int pick_shape(const Shape (&shapes)[N], uint32_t C, uint32_t B, Ok ok, uint32_t max_b = ~0u) {
+    for (size_t i = 0; i < N; ++i) {
+        const Shape &sh = shapes[i];
+        if ((!sh.C || sh.C == C) && (sh.B ? sh.B == B : B <= max_b) && (!sh.pf || B % 4 == 0) && ok(i)) return (int)i;
+    }
+    return -1;
+}
 constexpr uint32_t kSegMaxState = 1024;   // bytes of State a lane copies (the walk keeps one in LDS)
 constexpr uint32_t kSegWarm0 = 4;         // blocks of warm-up of a first render
 constexpr uint32_t kSegWarmBumps = 2;     // at most this many blocks added for a few misses
 constexpr uint32_t kSegWarmMax = 4096;    // the longest warm-up (blocks); past it, the chain is serial
-constexpr uint32_t kSegLevels = 4;        // warm-up levels a render may try (x16 each)
+constexpr uint32_t kSegLevels = dspb_max_levels;  // warm-up levels a render may try (x16 each)
 constexpr uint32_t kSegMinBlocks = 4;     // blocks per segment at least
 
-// Host mirror of the driver's argument block (same layout on both sides).
-struct RenderArgsG {
-    void *P;
-    void *S;
-    float *in[dspb::kMaxChannels];
-    float *out[dspb::kMaxChannels];
-    unsigned long long L;
-    unsigned long long nblocks;
-    unsigned long long block0;
-    unsigned in_ch;
-    unsigned C;
-    unsigned B;
-    float sr;
-    unsigned lds;  // path: stateful 1 = LDS double buffer; stateless 1/2 private, 3 LDS blocks
-    unsigned lds_nb;      // stateless LDS path: blocks per workgroup round
-    unsigned lds_stride;  // stateless LDS path: floats per block in LDS (C B + 1)
-    unsigned par;         // blocks render independently (dsp_module: par), in parallel
-};
-// Host mirror of kDriver's dspb_seg_args.
-struct SegArgsG {
-    RenderArgsG R;
-    void *st_blk;
-    void *st_end;
-    unsigned *list;
-    unsigned *count;
-    unsigned *prev_count;
-    unsigned char *flags;
-    unsigned *stats;
-    unsigned long long seg;
-    unsigned K;
-    unsigned warm;
-    unsigned prev_warm;
-    unsigned level;
-    unsigned mode;
-    unsigned pass;
-    unsigned exact;
-    unsigned long long perturb;
-    void *st_ind;
-    unsigned split;
-};
-
-// kDriver / kSegDriver: the driver kernels (csrc/plugin_driver.inl) and the
-// speculative-segment kernels (csrc/plugin_driver_seg.inl), as strings
+// kDriver / kSegDriver: plugin_driver_abi.h + the driver kernels
+// (csrc/plugin_driver.inl) and the speculative-segment kernels
+// (csrc/plugin_driver_seg.inl), as strings
 #include "plugin_driver_src.inc"
 
 struct ArenaHost {  // mirror of dspb_arena
@@ -153,32 +127,33 @@ struct dsp_module {
     int device = -1;
     hipModule_t mod = nullptr;
     hipModule_t chain_mod = nullptr;   // the State chain kernels from edited IR (dspb_chain_co), or NULL
-    // the LDS-blocks kernels (NULL for code objects compiled before they
-    // existed): [0] any (C, B), then the instantiations of kLdsShapes
-    hipFunction_t f_render_lds[7] = {};
-    hipFunction_t f_render_st[4] = {};  // kStShapes (NULL: dspb_render)
+    // the LDS-blocks kernels, as kLdsShapes (NULL for code objects compiled
+    // before they existed)
+    hipFunction_t f_render_lds[std::size(kLdsShapes)] = {};
+    hipFunction_t f_render_st[std::size(kStShapes)] = {};  // kStShapes (NULL: dspb_render)
     // speculative segments (kSegShapes, the check, kWalkShapes; NULL in code
     // objects compiled before them: the serial chain)
-    hipFunction_t f_seg[5] = {}, f_seg_rerun[5] = {}, f_seg_check = nullptr, f_seg_walk[2] = {};
+    hipFunction_t f_seg[std::size(kSegShapes)] = {}, f_seg_rerun[std::size(kSegShapes)] = {}, f_seg_check = nullptr,
+                  f_seg_walk[std::size(kWalkShapes)] = {};
     // kChainShapes and their private memory per lane: one whose compiled
     // form kept more than a State copy there kept (part of) the block, which
     // the State then depends on -- the serial chain renders instead
-    hipFunction_t f_seg_chain[4] = {};
-    int chain_priv[4] = {};
-    hipFunction_t f_seg_chain_ind[4] = {};  // kChainIndShapes (facts.state_split), private memory as above
-    int chain_ind_priv[4] = {};
+    hipFunction_t f_seg_chain[std::size(kChainShapes)] = {};
+    int chain_priv[std::size(kChainShapes)] = {};
+    hipFunction_t f_seg_chain_ind[std::size(kChainIndShapes)] = {};  // (facts.state_split), private memory as above
+    int chain_ind_priv[std::size(kChainIndShapes)] = {};
     struct SegWork {
         void *blk = nullptr;           // [cap_blk] States: st_blk
-        void *ind = nullptr;           // [cap_ind] States: a split State's independent words (st_ind, 4 K)
+        void *ind = nullptr;           // [cap_ind] States: a split State's independent words (st_ind, kSegLevels K)
         uint64_t cap_ind = 0;
         void *end = nullptr;           // [cap] States: st_end
         uint64_t cap_blk = 0;
         unsigned *list = nullptr;      // [cap]
         unsigned char *flags = nullptr;  // [cap]
-        unsigned *words = nullptr;     // [0] count, [4..8) stats
+        unsigned *words = nullptr;     // [DSPB_WORDS]: the listings' counts and stats (dspb_word_slot)
         uint32_t cap = 0;
         // the counters of the last two speculative renders: pinned copies
-        // [2][4], each behind an event, read back without waiting by a later
+        // [2][DSPB_STAT_PINNED], each behind an event, read back without waiting by a later
         // call (what the module learns) or waiting by dsp_module_state_spec
         unsigned *h_stats = nullptr;
         hipEvent_t ev[2] = {};
@@ -391,6 +366,7 @@ int dsp_module_compile(const char *source, const char *name, void **code, uint64
     const dspb::irp::Facts facts = analyze_source(source);
     tu += "extern \"C\" __attribute__((used, visibility(\"default\"))) __device__ const unsigned char "
           "dspb_callback_facts[] = {" + dspb::desc::hex_literal(dspb::irp::encode(facts)) + "};\n";
+    tu += "#define DSPB_ABI_STATE State\n";  // plugin_driver_abi.h, at the front of kDriver
     tu += kDriver;
     // the segment kernels only where they can run: a callback the analysis
     // bounded that writes its State (the loader treats them as optional)
@@ -526,40 +502,33 @@ int dsp_module_load(const void *code, uint64_t code_size, int device, dsp_module
                                                         {&m->f_callback, "dspb_callback"}};
     for (auto &f : fs)
         if ((e = hipModuleGetFunction(f.f, m->mod, f.n)) != hipSuccess) return fail(dspb::hip_fail(e, f.n));
-    for (int i = 0; i < 7; ++i) {
-        if (hipModuleGetFunction(&m->f_render_lds[i], m->mod, kLdsShapes[i].name) != hipSuccess) {
-            (void)hipGetLastError();
-            m->f_render_lds[i] = nullptr;
-        }
-    }
     auto optional = [&](hipFunction_t *f, const char *name) {
         if (hipModuleGetFunction(f, m->mod, name) != hipSuccess) {
             (void)hipGetLastError();
             *f = nullptr;
         }
     };
-    for (int i = 0; i < 4; ++i) optional(&m->f_render_st[i], kStShapes[i].name);
-    for (int i = 0; i < 5; ++i) {
+    // a chain kernel with its private memory per lane (all or nothing)
+    auto chain = [&](hipModule_t mod, hipFunction_t *f, int *priv, const char *name) {
+        hipFunction_t g = nullptr;
+        if (hipModuleGetFunction(&g, mod, name) != hipSuccess ||
+            hipFuncGetAttribute(priv, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, g) != hipSuccess) {
+            (void)hipGetLastError();
+            g = nullptr;
+        }
+        *f = g;
+    };
+    for (size_t i = 0; i < std::size(kLdsShapes); ++i) optional(&m->f_render_lds[i], kLdsShapes[i].name);
+    for (size_t i = 0; i < std::size(kStShapes); ++i) optional(&m->f_render_st[i], kStShapes[i].name);
+    for (size_t i = 0; i < std::size(kSegShapes); ++i) {
         optional(&m->f_seg[i], kSegShapes[i].name);
         if (kSegShapes[i].rerun) optional(&m->f_seg_rerun[i], kSegShapes[i].rerun);
     }
-    for (int i = 0; i < 2; ++i) optional(&m->f_seg_walk[i], kWalkShapes[i].name);
+    for (size_t i = 0; i < std::size(kWalkShapes); ++i) optional(&m->f_seg_walk[i], kWalkShapes[i].name);
     optional(&m->f_seg_check, "dspb_seg_check");
-    for (int i = 0; i < 4; ++i) {
-        optional(&m->f_seg_chain[i], kChainShapes[i].name);
-        if (m->f_seg_chain[i] &&
-            hipFuncGetAttribute(&m->chain_priv[i], HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, m->f_seg_chain[i]) !=
-                hipSuccess) {
-            (void)hipGetLastError();
-            m->f_seg_chain[i] = nullptr;
-        }
-        optional(&m->f_seg_chain_ind[i], kChainIndShapes[i].name);
-        if (m->f_seg_chain_ind[i] &&
-            hipFuncGetAttribute(&m->chain_ind_priv[i], HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, m->f_seg_chain_ind[i]) !=
-                hipSuccess) {
-            (void)hipGetLastError();
-            m->f_seg_chain_ind[i] = nullptr;
-        }
+    for (size_t i = 0; i < std::size(kChainShapes); ++i) {
+        chain(m->mod, &m->f_seg_chain[i], &m->chain_priv[i], kChainShapes[i].name);
+        chain(m->mod, &m->f_seg_chain_ind[i], &m->chain_ind_priv[i], kChainIndShapes[i].name);
     }
     {
         // the State chain kernels compiled from the callback's edited IR
@@ -571,19 +540,10 @@ int dsp_module_load(const void *code, uint64_t code_size, int device, dsp_module
             dspb::desc::code_symbol(code, code_size, "dspb_callback_facts", &ft)) {
             while (!ft.empty() && ft.back() == '\0') ft.pop_back();
             if (dspb::irp::decode(ft, &cf) && hipModuleLoadData(&m->chain_mod, cco.data()) == hipSuccess) {
-                auto from_chain = [&](hipFunction_t *f, int *priv, const char *name) {
-                    hipFunction_t g = nullptr;
-                    if (hipModuleGetFunction(&g, m->chain_mod, name) != hipSuccess ||
-                        hipFuncGetAttribute(priv, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, g) != hipSuccess) {
-                        (void)hipGetLastError();
-                        *f = nullptr;  // (the edited chain is all or nothing)
-                        return;
-                    }
-                    *f = g;
-                };
-                for (int i = 0; i < 4; ++i) {
-                    if (!cf.state_reads_block) from_chain(&m->f_seg_chain[i], &m->chain_priv[i], kChainShapes[i].name);
-                    from_chain(&m->f_seg_chain_ind[i], &m->chain_ind_priv[i], kChainIndShapes[i].name);
+                for (size_t i = 0; i < std::size(kChainShapes); ++i) {
+                    if (!cf.state_reads_block)
+                        chain(m->chain_mod, &m->f_seg_chain[i], &m->chain_priv[i], kChainShapes[i].name);
+                    chain(m->chain_mod, &m->f_seg_chain_ind[i], &m->chain_ind_priv[i], kChainIndShapes[i].name);
                 }
             } else {
                 (void)hipGetLastError();
@@ -729,7 +689,9 @@ int dsp_module_seg_timing(dsp_module *m, uint32_t out[8]) {
     std::memset(out, 0, 8 * sizeof(uint32_t));
     if (!m->seg.words) return DSP_OK;
     MOD_HIP(hipDeviceSynchronize());
-    MOD_HIP(hipMemcpy(out, m->seg.words + 24, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    static_assert(DSPB_STAT_WORDS - DSPB_STAT_TIMING == 8, "out[8]: the timing words");
+    MOD_HIP(hipMemcpy(out, m->seg.words + DSPB_WORD_STATS + DSPB_STAT_TIMING, 8 * sizeof(uint32_t),
+                      hipMemcpyDeviceToHost));
     return DSP_OK;
 }
 
@@ -1089,26 +1051,25 @@ int module_seg_collect(dsp_module *m, bool wait) {
         }
         W.pending[i] = false;
         dsp_state_spec_info &r = W.info[i];
-        const unsigned *h = W.h_stats + 16 * i;  // [0, 4) levels, [4] [5] reruns, [7] walk, [8, 12) levels run,
-                                                 // [12] the State chain ran
+        const unsigned *h = W.h_stats + DSPB_STAT_PINNED * i;  // (dspb_stat)
         const uint32_t first_warm = r.warmup_blocks;
         const bool spec = r.levels > 0;  // a speculative render (else the learnt State chain alone)
         uint32_t last = 0, warm = first_warm;
-        for (uint32_t L = 1; L < r.levels && h[8 + L]; ++L) {
+        for (uint32_t L = 1; L < r.levels && h[DSPB_STAT_LEVEL_RAN + L]; ++L) {
             last = L;
             warm = std::min<uint32_t>(warm * 16, kSegWarmMax);
         }
         if (spec) {
             r.levels = last + 1;
             r.warmup_blocks = warm;
-            r.differed[0] = h[last];
-            r.differed[1] = h[4];
-            r.differed[2] = h[5];
+            r.differed[0] = h[DSPB_STAT_LEVEL_DIFFERED + last];
+            r.differed[1] = h[DSPB_STAT_RERUN_DIFFERED];
+            r.differed[2] = h[DSPB_STAT_RERUN_DIFFERED + 1];
         }
-        r.serial_reruns = h[7];
-        r.chain = (h[12] || !spec) ? 1 : 0;
-        r.chain_mismatch = h[13];
-        r.chain_records_differed = h[14];
+        r.serial_reruns = h[DSPB_STAT_WALK_RERUNS];
+        r.chain = (h[DSPB_STAT_CHAINED] || !spec) ? 1 : 0;
+        r.chain_mismatch = h[DSPB_STAT_CHAIN_MISMATCH];
+        r.chain_records_differed = h[DSPB_STAT_CHAIN_RECORDS];
         // (split: set at launch, kept)
         if (W.seq[i] == W.calls) W.last = r;
         if (W.slot_gen[i] != W.gen) continue;  // rendered with other Parameters: nothing to learn
@@ -1150,84 +1111,77 @@ static bool module_rows_overlap(const float *const *in, uint32_t in_ch, uint64_t
     return false;
 }
 
-// A State-writing callback over the whole file as speculative segments
-// (kDriver dspb_segments); returns 1 (nothing launched) when the shape does
-// not fit them -- the caller renders the serial chain.  `chain` (a State
-// learned not to forget): the chain kernel records every block's State, and
-// the exact rerun renders the segments from them (dspb_seg_chain).
-static int module_render_seg(dsp_module *m, RenderArgsG &A, hipStream_t s, bool chain) {
-    const uint32_t C = A.C, B = A.B;
-    if (2ull * C * B * sizeof(float) > kStagedLdsBytes) return 1;  // the walk's double buffer
-    // the chain kernel of this shape, if its compiled form dropped the block
-    hipFunction_t fc = nullptr;
-    for (int i = 0; i < 4 && !fc; ++i)
-        if (m->f_seg_chain[i] && kChainShapes[i].C == C &&
-            (kChainShapes[i].B ? kChainShapes[i].B == B : B <= kChainMaxB) &&
-            (uint64_t)m->chain_priv[i] <= (uint64_t)m->state_size + 64)
-            fc = m->f_seg_chain[i];
-    if (chain && !fc) return 1;
-    hipFunction_t f = nullptr, fw = nullptr;
-    int fi = -1;
-    for (int i = 0; i < 5 && !f; ++i) {
-        const SegShape &sh = kSegShapes[i];
-        if (!m->f_seg[i] || (sh.C && sh.C != C) || (sh.B && sh.B != B) || (sh.pf && B % 4)) continue;
-        if (sh.rerun && !m->f_seg_rerun[i]) continue;
-        f = m->f_seg[fi = i];
-    }
-    if (!f) return 1;
-    // the pipelined kernels (dspb_segments_pf) stride blocks by C B + 2
-    const uint64_t stride = (uint64_t)C * B + (kSegShapes[fi].pf ? 2 : 1);
-    // lanes per workgroup (kDriver dspb_seg_nb: the same formula)
-    const uint64_t nb = std::min<uint64_t>(64, kLdsRoundBytes / (stride * sizeof(float)));
-    if (nb < 4) return 1;
-    for (int i = 0; i < 2 && !fw; ++i)
-        if (m->f_seg_walk[i] && (!kWalkShapes[i].C || kWalkShapes[i].C == C) &&
-            (!kWalkShapes[i].B || kWalkShapes[i].B == B))
-            fw = m->f_seg_walk[i];
-    if (!fw || !m->f_seg_check) return 1;
-    hipFunction_t fr = kSegShapes[fi].rerun ? m->f_seg_rerun[fi] : f;  // the reruns' kernel
-    auto &W = m->seg;
-    // segments: as many as the chip runs lanes at once (two workgroups per
-    // CU, nb lanes each), kSegMinBlocks blocks at least
-    const uint64_t lanes = kLdsWgPerCu * (uint64_t)m->cus * nb;
-    const uint64_t seg = std::max<uint64_t>((A.nblocks + lanes - 1) / lanes, kSegMinBlocks);
-    const uint64_t K = (A.nblocks + seg - 1) / seg;
-    // (block indices in 32 bits; one recorded State per block, at most 8 GB of them)
-    if (K < 2 || A.nblocks >= (1ull << 32) || A.nblocks * m->state_size > (8ull << 30)) return 1;
-    // a split State: the chain of its independent words, when the compiled
-    // kernel of the shape dropped the block (no private block: the words
-    // need no sample), and the records for it
-    hipFunction_t fsplit = nullptr;
+// ---- a State-writing callback over the whole file as speculative segments
+// (kSegDriver): the kernels of the shape, the workspaces, the
+// warm-up levels, then the launches.
+// The kernels of a speculative render of (C, B) and its geometry
+struct SegKernels {
+    hipFunction_t pass1 = nullptr, rerun = nullptr, walk = nullptr;
+    hipFunction_t chain = nullptr;  // the State chain, if the shape has one (dspb_seg_chain)
+    hipFunction_t split = nullptr;  // the chain of a split State's independent words (dspb_seg_chain_ind)
+    uint64_t stride = 0, nb = 0;    // floats per block in LDS, lanes per workgroup
+};
+// the chain kernel of a shape, if its compiled form dropped the block (its
+// private memory holds no more than a State copy)
+template <size_t N>
+static hipFunction_t chain_kernel(const dsp_module *m, const Shape (&shapes)[N], const hipFunction_t (&f)[N],
+                                  const int (&priv)[N], uint32_t C, uint32_t B) {
+    const int i = pick_shape(
+        shapes, C, B, [&](size_t j) { return f[j] && (uint64_t)priv[j] <= (uint64_t)m->state_size + 64; },
+        dspb_chain_max_b);
+    return i < 0 ? nullptr : f[i];
+}
+// false: the shape does not fit the segment kernels (`chain`: nor a State chain)
+static bool seg_kernels(const dsp_module *m, uint32_t C, uint32_t B, bool chain, SegKernels *k) {
+    if (2ull * C * B * sizeof(float) > kStagedLdsBytes) return false;  // the walk's double buffer
+    k->chain = chain_kernel(m, kChainShapes, m->f_seg_chain, m->chain_priv, C, B);
+    if (chain && !k->chain) return false;
+    const int fi = pick_shape(kSegShapes, C, B, [&](size_t i) {
+        return m->f_seg[i] && (!kSegShapes[i].rerun || m->f_seg_rerun[i]);
+    });
+    const int wi = pick_shape(kWalkShapes, C, B, [&](size_t i) { return m->f_seg_walk[i] != nullptr; });
+    if (fi < 0 || wi < 0 || !m->f_seg_check) return false;
+    k->pass1 = m->f_seg[fi];
+    k->rerun = kSegShapes[fi].rerun ? m->f_seg_rerun[fi] : k->pass1;
+    k->walk = m->f_seg_walk[wi];
+    k->stride = kSegShapes[fi].pf ? dspb_stride_pf(C, B) : dspb_stride(C, B);
+    k->nb = dspb_seg_nb(k->stride);
+    if (k->nb < 4) return false;
+    // a split State: the chain of its independent words (no private block:
+    // the words need no sample)
     if (!chain && m->facts.state_split)
-        for (int i = 0; i < 4 && !fsplit; ++i)
-            if (m->f_seg_chain_ind[i] && kChainIndShapes[i].C == C &&
-                (kChainIndShapes[i].B ? kChainIndShapes[i].B == B : B <= kChainMaxB) &&
-                (uint64_t)m->chain_ind_priv[i] <= (uint64_t)m->state_size + 64)
-                fsplit = m->f_seg_chain_ind[i];
-    if (fsplit && 4 * K > W.cap_ind) {
+        k->split = chain_kernel(m, kChainIndShapes, m->f_seg_chain_ind, m->chain_ind_priv, C, B);
+    return true;
+}
+// The workspaces of K segments over nblocks blocks; 1: no room for the
+// records (the serial chain renders this call).  Without room for a split
+// State's records only, *split is dropped: plain speculation.
+static int seg_grow(dsp_module *m, uint64_t K, uint64_t nblocks, hipFunction_t *split) {
+    auto &W = m->seg;
+    if (*split && kSegLevels * K > W.cap_ind) {
         if (int st = wait_uses(m)) return st;
         if (W.ind) (void)hipFree(W.ind);
         W.ind = nullptr;
         W.cap_ind = 0;
-        const uint64_t cap = std::max<uint64_t>(4 * K, 4096);
+        const uint64_t cap = std::max<uint64_t>(kSegLevels * K, 4096);
         if (hipMalloc(&W.ind, cap * m->state_size) != hipSuccess) {
             (void)hipGetLastError();
             W.ind = nullptr;
-            fsplit = nullptr;  // no room: plain speculation
+            *split = nullptr;
         } else {
             W.cap_ind = cap;
         }
     }
-    if (K > W.cap || A.nblocks > W.cap_blk) {
+    if (K > W.cap || nblocks > W.cap_blk) {
         if (int st = wait_uses(m)) return st;
         for (void *p : {W.blk, W.end, (void *)W.list, (void *)W.flags}) if (p) (void)hipFree(p);
         W.blk = W.end = nullptr, W.list = nullptr, W.flags = nullptr, W.cap = 0, W.cap_blk = 0;
         const uint32_t cap = (uint32_t)std::max<uint64_t>(K, 1024);
-        const uint64_t cap_blk = std::max<uint64_t>(A.nblocks, 4096);
+        const uint64_t cap_blk = std::max<uint64_t>(nblocks, 4096);
         if (hipMalloc(&W.blk, cap_blk * m->state_size) != hipSuccess ||
             hipMalloc(&W.end, (uint64_t)cap * m->state_size) != hipSuccess ||
             hipMalloc(&W.list, cap * sizeof(unsigned)) != hipSuccess || hipMalloc(&W.flags, cap) != hipSuccess) {
-            (void)hipGetLastError();  // no room for the records: the serial chain renders this call
+            (void)hipGetLastError();
             for (void *p : {W.blk, W.end, (void *)W.list, (void *)W.flags}) if (p) (void)hipFree(p);
             W.blk = W.end = nullptr, W.list = nullptr, W.flags = nullptr;
             return 1;
@@ -1236,10 +1190,120 @@ static int module_render_seg(dsp_module *m, RenderArgsG &A, hipStream_t s, bool 
         W.cap_blk = cap_blk;
     }
     if (!W.words) {
-        MOD_HIP(hipMalloc(&W.words, 32 * sizeof(unsigned)));
-        MOD_HIP(hipHostMalloc(&W.h_stats, 32 * sizeof(unsigned), hipHostMallocDefault));
+        MOD_HIP(hipMalloc(&W.words, DSPB_WORDS * sizeof(unsigned)));
+        MOD_HIP(hipHostMalloc(&W.h_stats, 2 * DSPB_STAT_PINNED * sizeof(unsigned), hipHostMallocDefault));
         for (hipEvent_t &e : W.ev) MOD_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
+    return DSP_OK;
+}
+// The warm-up of each level pass 1 may run: the learnt one, then 16x longer
+// ones while too many segments started wrong (each level decides on the GPU
+// whether it runs: dspb_seg_level_runs).  Returns how many.
+static uint32_t seg_levels(const dsp_module *m, uint64_t nblocks, uint64_t seg, bool has_chain,
+                           uint32_t (&lw)[kSegLevels]) {
+    uint32_t nlev = 0;
+    for (uint32_t L = 0, warm = m->seg.warm; L < kSegLevels; ++L) {
+        if (L > 0) {
+            const uint32_t next = std::min<uint32_t>(warm * 16, kSegWarmMax);
+            if (next <= warm || 2ull * next >= nblocks) break;  // no longer, or as long as the file
+            // with a State chain to fall back on, a level whose rounds (its
+            // warm-up and a segment of full callbacks) exceed 1/16 of the
+            // file costs more than the chain (the State arithmetic alone over
+            // every block) is likely to: not tried
+            if (has_chain && 16ull * (next + seg) > nblocks) break;
+            warm = next;
+        }
+        lw[nlev++] = warm;
+    }
+    // learnt: the first level meets the State (the later ones would only
+    // return at once, a launch each of pass 1, its check and the split
+    // chain): the first two levels alone -- the second one is there for
+    // a render whose input keeps the first from meeting the State (it
+    // unlearns this; without it such a render fell to the reruns and the
+    // walk's serial chain, 465 segments of a 20 s peak follower)
+    return m->seg.one_level ? std::min<uint32_t>(nlev, 2) : nlev;
+}
+// One render's launches.  `base` holds what every launch shares (the buffers,
+// the geometry, the split State's records, the test hook); each launch kind
+// names the fields its kernel reads besides (directly, or through
+// dspb_seg_level_runs / dspb_seg_skip); a field no kernel of the kind reads
+// stays zero.
+struct SegLaunch {
+    const dsp_module *m;
+    const SegKernels &k;
+    hipStream_t s;
+    dspb_seg_args base;
+    unsigned *words;
+    int go(hipFunction_t f, unsigned grid, unsigned block, unsigned lds, dspb_seg_args G) const {
+        void *args[] = {&G};
+        MOD_HIP(hipModuleLaunchKernel(f, grid, 1, 1, block, 1, 1, lds, s, args, nullptr));
+        return DSP_OK;
+    }
+    // pass 1 (mode 0) or a rerun of the listed segments / of every segment from the chain's records
+    int segments(hipFunction_t f, dspb_seg_args G) const {
+        return go(f, (unsigned)((base.K + k.nb - 1) / k.nb), 256, (unsigned)(k.nb * k.stride * sizeof(float)), G);
+    }
+    int pass1(unsigned level, unsigned warm, unsigned prev_warm) const {
+        dspb_seg_args G = base;
+        G.mode = 0, G.level = level, G.warm = warm, G.prev_warm = prev_warm, G.count = words + DSPB_WORD_COUNT;
+        return segments(k.pass1, G);
+    }
+    int rerun(unsigned exact, unsigned *count) const {
+        dspb_seg_args G = base;
+        G.mode = 1, G.exact = exact, G.count = count;
+        return segments(k.rerun, G);
+    }
+    // 4 segments per 256 threads; list = true: the differing segments are listed in `count` for a rerun.
+    // Pass 1's check (level != DSPB_NO_LEVEL) decides as pass 1 did whether the level runs: its prev_warm
+    int check(unsigned level, unsigned prev_warm, unsigned pass, bool list, unsigned exact, unsigned *count,
+              unsigned *prev_count) const {
+        dspb_seg_args G = base;
+        G.level = level, G.prev_warm = prev_warm, G.pass = pass, G.mode = list ? 1 : 0, G.exact = exact;
+        G.count = count, G.prev_count = prev_count;
+        return go(m->f_seg_check, (unsigned)((base.K + 3) / 4), 256, 0, G);
+    }
+    int walk(unsigned exact) const {
+        dspb_seg_args G = base;
+        G.exact = exact;
+        return go(k.walk, 1, 256, (unsigned)(2ull * base.R.C * base.R.B * sizeof(float)), G);
+    }
+    // mode 2: within a speculative render, only when level `level` would run (the one before failed)
+    int chain(unsigned mode, unsigned level, unsigned prev_warm) const {
+        dspb_seg_args G = base;
+        G.mode = mode, G.level = level, G.prev_warm = prev_warm;
+        return go(k.chain, 1, 64, 0, G);
+    }
+    int split_chain(unsigned level, unsigned warm, unsigned prev_warm) const {
+        dspb_seg_args G = base;
+        G.level = level, G.warm = warm, G.prev_warm = prev_warm;
+        return go(k.split, 1, 64, 0, G);
+    }
+    // every segment from the State chain's records, the records checked: every
+    // boundary against the State the segment before ended with, then the walk
+    // renders serially from the true State whatever differs and writes the
+    // live State (exact 2: each returns at once unless the chain ran)
+    int from_chain(unsigned exact) const {
+        if (int st = rerun(exact, nullptr)) return st;
+        if (int st = check(DSPB_NO_LEVEL, 0, DSPB_STAT_CHAIN_MISMATCH, false, exact, nullptr, nullptr)) return st;
+        return walk(exact);
+    }
+};
+// Returns 1 (nothing launched) when the shape does not fit the segments -- the
+// caller renders the serial chain.  `chain` (a State learned not to forget):
+// the chain kernel records every block's State, and the exact rerun renders
+// the segments from them (dspb_seg_chain).
+static int module_render_seg(dsp_module *m, dspb_render_args &A, hipStream_t s, bool chain) {
+    SegKernels k;
+    if (!seg_kernels(m, A.C, A.B, chain, &k)) return 1;
+    auto &W = m->seg;
+    // segments: as many as the chip runs lanes at once (two workgroups per
+    // CU, nb lanes each), kSegMinBlocks blocks at least
+    const uint64_t lanes = kLdsWgPerCu * (uint64_t)m->cus * k.nb;
+    const uint64_t seg = std::max<uint64_t>((A.nblocks + lanes - 1) / lanes, kSegMinBlocks);
+    const uint64_t K = (A.nblocks + seg - 1) / seg;
+    // (block indices in 32 bits; one recorded State per block, at most 8 GB of them)
+    if (K < 2 || A.nblocks >= (1ull << 32) || A.nblocks * m->state_size > (8ull << 30)) return 1;
+    if (int st = seg_grow(m, K, A.nblocks, &k.split)) return st;
     // the slot this call fills: the one of the render two calls back, whose
     // counters have landed by now in a stream of back-to-back calls
     const int slot = W.seq[0] <= W.seq[1] ? 0 : 1;
@@ -1247,127 +1311,62 @@ static int module_render_seg(dsp_module *m, RenderArgsG &A, hipStream_t s, bool 
         MOD_HIP(hipEventSynchronize(W.ev[slot]));
         if (int st = module_seg_collect(m, false)) return st;
     }
-    W.slot_one[slot] = false;  // (set below when the levels are cut to the first)
-    SegArgsG G{};
+    W.slot_one[slot] = false;  // (set below when the levels are cut to the first two)
+    SegLaunch q{m, k, s, {}, W.words};
+    dspb_seg_args &G = q.base;
     G.R = A;
-    G.R.lds_nb = (unsigned)nb;
-    G.R.lds_stride = (unsigned)stride;
+    G.R.lds_nb = (unsigned)k.nb;
+    G.R.lds_stride = (unsigned)k.stride;
     G.st_blk = W.blk;
     G.st_end = W.end;
     G.list = W.list;
     G.flags = W.flags;
-    G.stats = W.words + 8;  // words: [0] pass 1's listing, [2] / [3] the reruns' listings
+    G.stats = W.words + DSPB_WORD_STATS;
     G.seg = seg;
     G.K = (unsigned)K;
-    void *args[] = {&G};
-    const unsigned lds = (unsigned)(nb * stride * sizeof(float));
-    const unsigned gseg = (unsigned)((K + nb - 1) / nb), gchk = (unsigned)((K + 3) / 4);  // 4 segments per 256 threads
-    G.perturb = chain || fc || fsplit ? W.perturb : 0;  // (test hook: consumed by the render that may run a chain)
+    G.perturb = chain || k.chain || k.split ? W.perturb : 0;  // (test hook: consumed by the render that may run a chain)
     if (G.perturb) W.perturb = 0;
-    MOD_HIP(hipMemsetAsync(W.words, 0, 32 * sizeof(unsigned), s));
-    // the State chain's records checked: every boundary against the State the
-    // segment before ended with (stats[13]), then the walk renders serially
-    // from the true State whatever differs and writes the live State
-    auto checked = [&](unsigned exact) -> int {
-        G.exact = exact;
-        G.mode = 0;
-        G.pass = 13;
-        G.level = 0xffffffffu;
-        MOD_HIP(hipModuleLaunchKernel(m->f_seg_check, gchk, 1, 1, 256, 1, 1, 0, s, args, nullptr));
-        MOD_HIP(hipModuleLaunchKernel(fw, 1, 1, 1, 256, 1, 1, (unsigned)(2ull * C * B * sizeof(float)), s, args,
-                                      nullptr));
-        return DSP_OK;
-    };
+    if (k.split) {  // pass 1 starts every warm-up from the split chain's words (the others from the live State)
+        G.st_ind = W.ind;
+        G.split = 1;
+    }
+    MOD_HIP(hipMemsetAsync(W.words, 0, DSPB_WORDS * sizeof(unsigned), s));
     uint32_t levels = 0;
     if (chain) {
-        G.mode = 1;
-        MOD_HIP(hipModuleLaunchKernel(fc, 1, 1, 1, 64, 1, 1, 0, s, args, nullptr));
-        G.exact = 1;
-        MOD_HIP(hipModuleLaunchKernel(fr, gseg, 1, 1, 256, 1, 1, lds, s, args, nullptr));
-        if (int st = checked(1)) return st;
+        if (int st = q.chain(1, 0, 0)) return st;
+        if (int st = q.from_chain(1)) return st;
     } else {
-        // a split State: its independent words' chain first, pass 1 then
-        // starts every warm-up from them (the other words from the live State)
-        // the warm-up of each level pass 1 may run: the learnt one, then 16x
-        // longer ones while too many segments started wrong (each level
-        // decides on the GPU whether it runs: dspb_seg_level_runs)
-        uint32_t lw[kSegLevels] = {}, nlev = 0;
-        for (uint32_t L = 0, warm = W.warm; L < kSegLevels; ++L) {
-            if (L > 0) {
-                const uint32_t next = std::min<uint32_t>(warm * 16, kSegWarmMax);
-                if (next <= warm || 2ull * next >= A.nblocks) break;  // no longer, or as long as the file
-                // with a State chain to fall back on, a level whose rounds (its
-                // warm-up and a segment of full callbacks) exceed 1/16 of the
-                // file costs more than the chain (the State arithmetic alone over
-                // every block) is likely to: not tried
-                if (fc && 16ull * (next + seg) > A.nblocks) break;
-                warm = next;
-            }
-            lw[nlev++] = warm;
-        }
-        // learnt: the first level meets the State (the later ones would only
-        // return at once, a launch each of pass 1, its check and the split
-        // chain): the first two levels alone -- the second one is there for
-        // a render whose input keeps the first from meeting the State (it
-        // unlearns this; without it such a render fell to the reruns and the
-        // walk's serial chain, 465 segments of a 20 s peak follower)
-        if (W.one_level) nlev = std::min<uint32_t>(nlev, 2);
+        uint32_t lw[kSegLevels] = {};
+        levels = seg_levels(m, A.nblocks, seg, k.chain != nullptr, lw);
         W.slot_one[slot] = W.one_level;
-        if (fsplit) {
-            G.st_ind = W.ind;
-            G.split = 1;
-        }
-        uint32_t warm = W.warm, prev = 0;
-        G.count = W.words;
-        for (uint32_t L = 0; L < nlev; ++L) {
-            prev = L ? lw[L - 1] : 0;
-            warm = lw[L];
-            G.level = L;
-            G.warm = warm;
-            G.prev_warm = prev;
+        for (uint32_t L = 0; L < levels; ++L) {
+            const uint32_t prev = L ? lw[L - 1] : 0;
             // a split State: the chain of its independent words first, recording
             // them where this level's warm-ups start (it runs only where the
-            // level does); pass 1 starts from them and the live State's others
-            if (fsplit) MOD_HIP(hipModuleLaunchKernel(fsplit, 1, 1, 1, 64, 1, 1, 0, s, args, nullptr));
-            G.mode = 0;
-            MOD_HIP(hipModuleLaunchKernel(f, gseg, 1, 1, 256, 1, 1, lds, s, args, nullptr));
-            G.pass = L;
-            G.mode = 1;  // the check lists the differing segments for the rerun
-            MOD_HIP(hipModuleLaunchKernel(m->f_seg_check, gchk, 1, 1, 256, 1, 1, 0, s, args, nullptr));
-            ++levels;
+            // level does)
+            if (k.split)
+                if (int st = q.split_chain(L, lw[L], prev)) return st;
+            if (int st = q.pass1(L, lw[L], prev)) return st;
+            if (int st = q.check(L, prev, DSPB_STAT_LEVEL_DIFFERED + L, true, 0, W.words + DSPB_WORD_COUNT, nullptr)) return st;
         }
         // the last level failed (decided on the GPU): the State chain and the
         // exact rerun take over, the reruns and the walk below return at once
-        if (fc) {
-            G.level = levels;
-            G.prev_warm = warm;
-            G.mode = 2;
-            MOD_HIP(hipModuleLaunchKernel(fc, 1, 1, 1, 64, 1, 1, 0, s, args, nullptr));
-        }
+        if (k.chain)  // (levels >= 1: level 0 is always planned)
+            if (int st = q.chain(2, levels, lw[levels - 1])) return st;
         // two reruns of the listed segments, each checked; the last check only flags
-        G.level = 0xffffffffu;
-        unsigned *listing = W.words;
+        unsigned *listing = W.words + DSPB_WORD_COUNT;
         for (unsigned p = 0; p < 2; ++p) {
-            G.count = listing;
-            G.mode = 1;
-            MOD_HIP(hipModuleLaunchKernel(fr, gseg, 1, 1, 256, 1, 1, lds, s, args, nullptr));
-            G.prev_count = listing;
-            listing = W.words + 2 + p;
-            G.count = listing;
-            G.pass = 4 + p;
-            G.mode = p == 0 ? 1 : 0;
-            MOD_HIP(hipModuleLaunchKernel(m->f_seg_check, gchk, 1, 1, 256, 1, 1, 0, s, args, nullptr));
+            unsigned *next = W.words + DSPB_WORD_RERUN_COUNT + p;
+            if (int st = q.rerun(0, listing)) return st;
+            if (int st = q.check(DSPB_NO_LEVEL, 0, DSPB_STAT_RERUN_DIFFERED + p, p == 0, 0, next, listing)) return st;
+            listing = next;
         }
-        MOD_HIP(hipModuleLaunchKernel(fw, 1, 1, 1, 256, 1, 1, (unsigned)(2ull * C * B * sizeof(float)), s, args,
-                                      nullptr));
-        if (fc) {  // (each returns at once unless the chain ran)
-            G.mode = 1;
-            G.exact = 2;
-            MOD_HIP(hipModuleLaunchKernel(fr, gseg, 1, 1, 256, 1, 1, lds, s, args, nullptr));
-            if (int st = checked(2)) return st;
-        }
+        if (int st = q.walk(0)) return st;
+        if (k.chain)
+            if (int st = q.from_chain(2)) return st;
     }
-    MOD_HIP(hipMemcpyAsync(W.h_stats + 16 * slot, W.words + 8, 16 * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    MOD_HIP(hipMemcpyAsync(W.h_stats + DSPB_STAT_PINNED * slot, G.stats, DSPB_STAT_PINNED * sizeof(unsigned),
+                           hipMemcpyDeviceToHost, s));
     MOD_HIP(hipEventRecord(W.ev[slot], s));
     W.pending[slot] = true;
     W.seq[slot] = ++W.calls;
@@ -1380,7 +1379,7 @@ static int module_render_seg(dsp_module *m, RenderArgsG &A, hipStream_t s, bool 
     r.warmup_blocks = chain ? 0 : W.warm;  // the first level's; module_seg_collect names the one that stood
     r.levels = levels;                     // 0: the learnt State chain alone
     r.chain = chain ? 1 : 0;
-    r.split = fsplit ? 1 : 0;
+    r.split = k.split ? 1 : 0;
     MOD_HIP(hipEventRecord(m->use_ev, s));
     return DSP_OK;
 }
@@ -1415,7 +1414,7 @@ int module_render(dsp_module *m, const void *params, uint32_t params_size, const
     }
     std::lock_guard<std::mutex> lk(m->mu);
     if (int st = upload_params(m, params, params_size, s)) return st;
-    RenderArgsG A{};
+    dspb_render_args A{};
     A.P = m->d_params;
     A.S = m->d_state[0];
     for (uint32_t c = 0; c < in_ch; ++c) A.in[c] = const_cast<float *>(in[c]);
@@ -1435,24 +1434,14 @@ int module_render(dsp_module *m, const void *params, uint32_t params_size, const
         // default: the LDS-blocks path (dspb_render_lds) when a round of at
         // least 4 blocks fits the per-workgroup LDS budget, else the
         // in-place wave path; DSPB_STATELESS_PATH=0/3 forces one
-        uint64_t stride = (uint64_t)C * B + 1;
-        // the most specific instantiation for (C, B): exact shapes first (the
-        // software-pipelined rounds of dspb_stateless_lds_pf, on a persistent
-        // grid of two workgroups per CU)
-        hipFunction_t f = nullptr;
-        bool persistent = false;
-        for (int i = 6; i >= 0 && !f; --i)
-            if (m->f_render_lds[i] && kLdsShapes[i].C == C && kLdsShapes[i].B == B) {
-                f = m->f_render_lds[i];
-                persistent = B % 4 == 0;
-            }
-        for (int i = 6; i >= 0 && !f; --i)
-            if (m->f_render_lds[i] && (!kLdsShapes[i].C || kLdsShapes[i].C == C) && !kLdsShapes[i].B)
-                f = m->f_render_lds[i];
-        // rounds of nb blocks at a block stride of C B + 1 floats, C B + 2 for
-        // the pipelined kernels (kDriver dspb_lds_nb: the same formula)
-        if (persistent) stride = (uint64_t)C * B + 2;
-        const uint64_t nb = std::min<uint64_t>(64, kLdsRoundBytes / (stride * sizeof(float)) / 4 * 4);
+        // the most specific instantiation for (C, B); a constant shape runs
+        // the software-pipelined rounds of dspb_stateless_lds_pf, on a
+        // persistent grid of two workgroups per CU
+        const int fi = pick_shape(kLdsShapes, C, B, [&](size_t i) { return m->f_render_lds[i] != nullptr; });
+        hipFunction_t f = fi < 0 ? nullptr : m->f_render_lds[fi];
+        const bool persistent = fi >= 0 && dspb_lds_pipelined(kLdsShapes[fi].C, kLdsShapes[fi].B);
+        const uint64_t stride = persistent ? dspb_stride_pf(C, B) : dspb_stride(C, B);
+        const uint64_t nb = dspb_lds_nb(stride);  // blocks per round
         int path = stateless_path_forced();
         if (path < 0) path = nb >= 4 ? 3 : 0;
         if (path == 3 && (nb < 4 || !f)) path = 0;
@@ -1505,11 +1494,8 @@ int module_render(dsp_module *m, const void *params, uint32_t params_size, const
         A.lds = 1;
         block = 256;
         lds_bytes = (unsigned)(2ull * C * B * sizeof(float));
-        for (int i = 0; i < 4; ++i)
-            if (m->f_render_st[i] && kStShapes[i].C == C && (!kStShapes[i].B || kStShapes[i].B == B)) {
-                f = m->f_render_st[i];
-                break;
-            }
+        const int fi = pick_shape(kStShapes, C, B, [&](size_t i) { return m->f_render_st[i] != nullptr; });
+        if (fi >= 0) f = m->f_render_st[fi];
     }
     MOD_HIP(hipModuleLaunchKernel(f, grid, 1, 1, block, 1, 1, lds_bytes, s, args, nullptr));
     MOD_HIP(hipEventRecord(m->use_ev, s));
@@ -1530,7 +1516,7 @@ int module_callback_once(dsp_module *m, const void *params, uint32_t params_size
     if (int st = check_device(m)) return st;
     std::lock_guard<std::mutex> lk(m->mu);
     if (int st = upload_params(m, params, params_size, s)) return st;
-    RenderArgsG A{};
+    dspb_render_args A{};
     A.P = m->d_params;
     A.S = m->d_state[0];
     for (uint32_t c = 0; c < C; ++c) A.out[c] = bufs[c];
@@ -1562,7 +1548,7 @@ int module_ir(dsp_module *m, const void *params, uint32_t params_size, float *co
     std::lock_guard<std::mutex> lk(m->mu);
     int st = init_slot(m, 1, params, C, sr, 16ull << 20, s);
     if (st) return st;
-    RenderArgsG A{};
+    dspb_render_args A{};
     A.P = m->d_params;
     A.S = m->d_state[1];
     for (uint32_t c = 0; c < C; ++c) A.out[c] = bufs[c];
@@ -1752,7 +1738,7 @@ int module_specialize(dsp_module *m, const void *params, uint32_t params_size, u
     } fr{&d};
     MOD_HIP(hipMemcpyAsync(d, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice, s));
     for (int p = 0; p < kProbes; ++p) {
-        RenderArgsG A{};
+        dspb_render_args A{};
         A.P = m->d_params;
         A.S = m->d_state[0];
         for (uint32_t c = 0; c < C; ++c) A.out[c] = d + (uint64_t)(p * C + c) * B;

@@ -3,25 +3,9 @@
 // descriptor, in one hiprtc translation unit for gfx950).  A source fragment,
 // not a translation unit of the library: it uses the plugin's Parameters,
 // State and audio_callback.  Embedded as a string by the Makefile
-// (build/gen/plugin_driver_src.inc); the host mirrors of its argument blocks
-// are module.cpp's RenderArgsG / SegArgsG.
-struct dspb_render_args {
-    void *P;
-    void *S;
-    float *in[16];
-    float *out[16];
-    unsigned long long L;
-    unsigned long long nblocks;
-    unsigned long long block0;
-    unsigned in_ch;
-    unsigned C;
-    unsigned B;
-    float sr;
-    unsigned lds;
-    unsigned lds_nb;
-    unsigned lds_stride;
-    unsigned par;
-};
+// (build/gen/plugin_driver_src.inc) behind plugin_driver_abi.h: the argument
+// blocks, the round geometry, the counters' slots and the kernel lists that
+// the host (module.cpp) shares.
 extern "C" __global__ void dspb_sizes(unsigned *o) {
     o[0] = sizeof(Parameters);
     o[1] = sizeof(State);
@@ -35,8 +19,7 @@ extern "C" __global__ void dspb_init(Parameters *p, State *s, unsigned C, float 
 }
 // one block: the render_audio body (audio.cpp:13-175), one-shot
 __device__ static void dspb_block(const dspb_render_args &A, unsigned long long b, State &st) {
-    float *ptrs[16];
-    const unsigned long long s0 = (A.block0 + b) * A.B;  // global sample of the block
+    float *ptrs[dspb_max_channels];
     for (unsigned c = 0; c < A.C; ++c) {
         ptrs[c] = A.out[c] + b * A.B;
         for (unsigned s = 0; s < A.B; ++s) {
@@ -44,7 +27,6 @@ __device__ static void dspb_block(const dspb_render_args &A, unsigned long long 
             ptrs[c][s] = (c < A.in_ch && i < A.L) ? A.in[c][i] : 0.0f;
         }
     }
-    (void)s0;
     audio_callback(*(Parameters *)A.P, st, ptrs, A.C, A.B, A.sr);
 }
 // render_audio's copy of block b into a staging buffer (zero past EOF and
@@ -130,7 +112,7 @@ __device__ static void dspb_stateless(const dspb_render_args &A) {
         }
         __syncthreads();  // the wave's copies are visible to every lane
         if (t < nb) {
-            float *ptrs[CC ? CC : 16];
+            float *ptrs[CC ? CC : dspb_max_channels];
             for (unsigned c = 0; c < C; ++c) ptrs[c] = dspb_global(A.out[c] + (i0 + (unsigned long long)t * A.B));
             audio_callback(prm, local.get(), ptrs, C, A.B, A.sr);
         }
@@ -160,7 +142,7 @@ __device__ static void dspb_stateful_lds(const dspb_render_args &A) {
     for (unsigned long long b = 0; b < A.nblocks; ++b) {
         float *cur = (b & 1) ? buf1 : buf0, *oth = (b & 1) ? buf0 : buf1;
         if (t == 0) {
-            float *ptrs[CC ? CC : 16];
+            float *ptrs[CC ? CC : dspb_max_channels];
             for (unsigned c = 0; c < C; ++c) ptrs[c] = cur + c * B;
             if constexpr (kLocal) audio_callback(prm, local, ptrs, C, B, A.sr);
             else audio_callback(prm, *gst, ptrs, C, B, A.sr);
@@ -174,6 +156,18 @@ __device__ static void dspb_stateful_lds(const dspb_render_args &A) {
         if (t == 0) __builtin_memcpy((void *)gst, (const void *)&local, sizeof(State));
     }
     dspb_stage_out(A, A.nblocks - 1, (A.nblocks - 1) & 1 ? buf1 : buf0, t, nt);
+}
+#define DSPB_INLINE_MEMBER __device__ __attribute__((always_inline))
+#define DSPB_INLINE DSPB_INLINE_MEMBER static inline
+// a float4 of a block row in LDS, as two float2 (rows at dspb_stride_pf are
+// 8-byte aligned)
+DSPB_INLINE void dspb_lds_put4(float *d, const float4 &v) {
+    ((float2 *)d)[0] = make_float2(v.x, v.y);
+    ((float2 *)d)[1] = make_float2(v.z, v.w);
+}
+DSPB_INLINE float4 dspb_lds_get4(const float *d) {
+    const float2 lo = ((const float2 *)d)[0], hi = ((const float2 *)d)[1];
+    return make_float4(lo.x, lo.y, hi.x, hi.y);
 }
 // no state, LDS blocks: a workgroup renders lds_nb consecutive blocks per
 // round.  render_audio's copy (audio.cpp:13-175: the file at the cursor,
@@ -235,7 +229,7 @@ __device__ static void dspb_stateless_lds(const dspb_render_args &A) {
         // whatever the active lanes, so the callbacks share as few as possible)
         if (t < nb) {
             float *blk = dspb_lbuf + t * SB;
-            float *ptrs[CC ? CC : 16];
+            float *ptrs[CC ? CC : dspb_max_channels];
             for (unsigned c = 0; c < C; ++c) ptrs[c] = blk + c * B;
             audio_callback(prm, local.get(), ptrs, C, B, A.sr);
         }
@@ -260,19 +254,6 @@ __device__ static void dspb_stateless_lds(const dspb_render_args &A) {
         __syncthreads();
     }
 }
-// blocks per round of the LDS-blocks path at a block stride of SB floats, a
-// multiple of 4 (18 blocks of stereo B = 512 instead of 16 made the
-// stateless rounds 1-6% slower, profiles/r05_lds_nb_ab.txt), and lanes of
-// the segment kernels: as many as the round's LDS holds (18 instead of 16:
-// 15% faster).  The host computes the same (module_render, module_render_seg)
-constexpr unsigned dspb_lds_nb(unsigned SB) {
-    const unsigned v = DSPB_LDS_ROUND_BYTES / (SB * 4u) / 4u * 4u;
-    return v < 64u ? v : 64u;
-}
-constexpr unsigned dspb_seg_nb(unsigned SB) {
-    const unsigned v = DSPB_LDS_ROUND_BYTES / (SB * 4u);
-    return v < 64u ? v : 64u;
-}
 // the LDS-blocks path for a constant shape (C, B, 4 | B), software
 // pipelined over the workgroup's rounds: a persistent grid of two
 // workgroups per CU walks the file, and while round r's callbacks run in LDS,
@@ -287,7 +268,7 @@ constexpr unsigned dspb_seg_nb(unsigned SB) {
 template <unsigned CC, unsigned BB>
 __device__ static void dspb_stateless_lds_pf(const dspb_render_args &A) {
     extern __shared__ float dspb_lbuf[];
-    constexpr unsigned C = CC, B = BB, SB = C * B + 2u, NB = dspb_lds_nb(SB);
+    constexpr unsigned C = CC, B = BB, SB = dspb_stride_pf(C, B), NB = dspb_lds_nb(SB);
     constexpr unsigned N4 = NB * B / 4u, PT = (N4 + 255u) / 256u;  // float4 per channel per round / per thread
     static_assert(NB <= 64 && B % 4 == 0, "one wave runs a round's callbacks");
     typedef __attribute__((address_space(1))) float4 gfloat4;
@@ -330,11 +311,7 @@ __device__ static void dspb_stateless_lds_pf(const dspb_render_args &A) {
 #pragma unroll
                 for (unsigned k = 0; k < PT; ++k) {
                     const unsigned j = 4u * (t + 256u * k);
-                    if (N4 % 256u == 0 || j < 4u * N4) {
-                        float2 *d = (float2 *)(dspb_lbuf + (j / B) * SB + c * B + j % B);
-                        d[0] = make_float2(pf[c][k].x, pf[c][k].y);
-                        d[1] = make_float2(pf[c][k].z, pf[c][k].w);
-                    }
+                    if (N4 % 256u == 0 || j < 4u * N4) dspb_lds_put4(dspb_lbuf + (j / B) * SB + c * B + j % B, pf[c][k]);
                 }
             }
         } else {  // render_audio's copy with zeros past EOF and for missing channels
@@ -362,11 +339,7 @@ __device__ static void dspb_stateless_lds_pf(const dspb_render_args &A) {
             if ((((unsigned long long)A.out[c]) & 15) == 0) {
                 gfloat4 *o4 = (gfloat4 *)(A.out[c] + i0);
 #pragma unroll 4
-                for (unsigned j = 4u * t; j < n; j += 1024u) {
-                    const float2 *d = (const float2 *)(dspb_lbuf + (j / B) * SB + c * B + j % B);
-                    const float2 lo = d[0], hi = d[1];
-                    o4[j / 4u] = make_float4(lo.x, lo.y, hi.x, hi.y);
-                }
+                for (unsigned j = 4u * t; j < n; j += 1024u) o4[j / 4u] = dspb_lds_get4(dspb_lbuf + (j / B) * SB + c * B + j % B);
             } else {
                 dspb_gfloat *o = (dspb_gfloat *)A.out[c] + i0;
                 for (unsigned j = t; j < n; j += 256u) o[j] = dspb_lbuf[(j / B) * SB + c * B + j % B];
@@ -385,17 +358,11 @@ __device__ static void dspb_stateless_lds_pf(const dspb_render_args &A) {
     extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void name(  \
         dspb_render_args A) {                                                          \
         if (A.par) {                                                                   \
-            if constexpr (CC > 0 && BB > 0 && BB % 4 == 0) dspb_stateless_lds_pf<CC, BB>(A); \
+            if constexpr (dspb_lds_pipelined(CC, BB)) dspb_stateless_lds_pf<CC, BB>(A); \
             else dspb_stateless_lds<CC, BB>(A);                                        \
         }                                                                              \
     }
-DSPB_LDS_KERNEL(dspb_render_lds_c2b512, 2, 512)
-DSPB_LDS_KERNEL(dspb_render_lds_c2b256, 2, 256)
-DSPB_LDS_KERNEL(dspb_render_lds_c2b1024, 2, 1024)
-DSPB_LDS_KERNEL(dspb_render_lds_c1b512, 1, 512)
-DSPB_LDS_KERNEL(dspb_render_lds_c1, 1, 0)
-DSPB_LDS_KERNEL(dspb_render_lds_c2, 2, 0)
-DSPB_LDS_KERNEL(dspb_render_lds, 0, 0)
+DSPB_LDS_KERNELS(DSPB_LDS_KERNEL)
 extern "C" __global__ void dspb_render(dspb_render_args A) {
     extern __shared__ float dspb_lbuf[];
     if (A.par) {
@@ -428,14 +395,11 @@ extern "C" __global__ void dspb_render(dspb_render_args A) {
         extern __shared__ float dspb_lbuf[];                                           \
         if (!A.par && blockIdx.x == 0) dspb_stateful_lds<CC, BB>(A);                   \
     }
-DSPB_ST_KERNEL(dspb_render_st_c2b512, 2, 512)
-DSPB_ST_KERNEL(dspb_render_st_c2b256, 2, 256)
-DSPB_ST_KERNEL(dspb_render_st_c1, 1, 0)
-DSPB_ST_KERNEL(dspb_render_st_c2, 2, 0)
+DSPB_ST_KERNELS(DSPB_ST_KERNEL)
 
 // compute_IR (plugin.cpp:17-58): the callback once, on buffers as they are
 extern "C" __global__ void dspb_callback(dspb_render_args A) {
-    float *ptrs[16];
+    float *ptrs[dspb_max_channels];
     for (unsigned c = 0; c < A.C; ++c) ptrs[c] = A.out[c];
     audio_callback(*(Parameters *)A.P, *(State *)A.S, ptrs, A.C, A.B, A.sr);
 }

@@ -22,38 +22,7 @@
 // still differs, so the result is the serial chain's whatever the plugin
 // does.  Filters forget their State: their trajectories from different States
 // meet bit for bit within a few hundred samples, and one pass suffices.
-struct dspb_seg_args {
-    dspb_render_args R;
-    State *st_blk;          // [nblocks] the State each block was rendered from
-    State *st_end;          // [K] the State each segment ended with
-    unsigned *list;         // segments to rerun (check -> rerun)
-    unsigned *count;        // how many
-    unsigned *prev_count;   // a rerun's check: the rerun's count (0: nothing changed, skip)
-    unsigned char *flags;   // the last check: 1 = differed
-    unsigned *stats;        // [0, 4) segments that differed per warm-up level, [4] / [5] after
-                            // rerun 1 / 2, [7] serial reruns of the walk, [8, 12) levels run,
-                            // [12] the State chain took over from the levels (dspb_seg_chain),
-                            // [13] segments whose first State (the chain's record) differed from
-                            // the State the segment before ended with, [14] blocks whose State in
-                            // the exact rerun differed from the chain's record
-    unsigned long long seg; // blocks per segment
-    unsigned K;             // segments
-    unsigned warm;          // pass 1: warm-up blocks
-    unsigned prev_warm;     // pass 1 at level > 0: the warm-up of the level before
-    unsigned level;         // pass 1 / its check: the warm-up level (~0u: a rerun's check)
-    unsigned mode;          // segments: 0 = pass 1 (every segment), 1 = rerun the listed ones;
-                            // check: 1 = list the differing ones for a rerun (0: flag only)
-    unsigned pass;          // the check's stats slot
-    unsigned exact;         // a rerun of every segment from the States the chain kernel recorded
-                            // (dspb_seg_chain): no list, no early stop (2: only if the chain ran);
-                            // the check and the walk after it: every segment boundary
-    unsigned long long perturb;  // test hook (dsp_module_debug): the chain kernel flips a bit of the
-                                 // State it recorded for block perturb - 1 (0: none)
-    State *st_ind;          // [4][K] a split State's block-independent words where pass 1 at each
-                            // warm-up level starts segment k's warm-up (dspb_seg_chain_ind); the
-                            // other words are not written
-    unsigned split;         // pass 1 starts each segment's warm-up from st_ind's words
-};
+// (the argument block dspb_seg_args and the counters' slots: plugin_driver_abi.h)
 // a split State (dsp_callback_facts.state_split): the 4-byte words a store of
 // a block-dependent value may hit (dsp_module_compile defines the list from
 // the callback's facts; -1: none; -(T + 2): every word from T on)
@@ -66,7 +35,16 @@ __device__ static constexpr bool dspb_word_dep(unsigned w) {
         if (d == (int)w || (d <= -2 && (int)w >= -d - 2)) return true;  // (-(T + 2): every word from T on)
     return false;
 }
+// a State's words: accesses that may alias the State's own fields (without
+// may_alias, type-based alias analysis lets the compiler take a word copy of
+// a State of doubles for unrelated memory -- and drop the callback's updates)
+typedef unsigned __attribute__((may_alias)) dspb_word;
+// a State as units: whole words where its size and alignment allow, else bytes
 constexpr bool kStateWords = sizeof(State) % 4 == 0 && alignof(State) >= 4;
+template <bool kWords> struct dspb_unit_of { typedef dspb_word type; };
+template <> struct dspb_unit_of<false> { typedef unsigned char type; };
+typedef dspb_unit_of<kStateWords>::type dspb_unit;
+constexpr unsigned kStateUnits = sizeof(State) / sizeof(dspb_unit);
 __device__ static constexpr unsigned dspb_first_ind_word() {
     for (unsigned i = 0; i < sizeof(State) / 4; ++i)
         if (!dspb_word_dep(i)) return i;
@@ -74,7 +52,7 @@ __device__ static constexpr unsigned dspb_first_ind_word() {
 }
 // the State chain took over within this render: the reruns, their checks and
 // the walk have nothing to do
-__device__ static bool dspb_seg_chained(const dspb_seg_args &G) { return *(volatile unsigned *)&G.stats[12] != 0; }
+__device__ static bool dspb_seg_chained(const dspb_seg_args &G) { return *(volatile unsigned *)&G.stats[DSPB_STAT_CHAINED] != 0; }
 // a rerun, check or walk launch with nothing to do: those after the State
 // chain (G.exact: 1 always, 2 only when the chain ran in this render) and the
 // speculative ones (only when it did not)
@@ -89,39 +67,23 @@ __device__ static bool dspb_seg_level_runs(const dspb_seg_args &G) {
     if (G.level == 0) return true;
     const volatile unsigned *st = G.stats;
     const unsigned prev = G.level - 1;
-    if (!st[8 + prev]) return false;
+    if (!st[DSPB_STAT_LEVEL_RAN + prev]) return false;
     const unsigned long long early = G.prev_warm / G.seg < G.K - 1 ? G.prev_warm / G.seg : G.K - 1;
     const unsigned long long guessed = G.K - 1 - early;
-    return guessed && st[prev] * 8ull > guessed;
+    return guessed && st[DSPB_STAT_LEVEL_DIFFERED + prev] * 8ull > guessed;
 }
-// a State's words: accesses that may alias the State's own fields (without
-// may_alias, type-based alias analysis lets the compiler take a word copy of
-// a State of doubles for unrelated memory -- and drop the callback's updates)
-typedef unsigned __attribute__((may_alias)) dspb_word;
-// a State copy as whole words, fully unrolled (a private State stays in
+// a State copy unit by unit, fully unrolled (a private State stays in
 // registers; a memcpy this size would be lowered to a loop over it)
 __device__ static inline void dspb_copy_state(void *dst, const void *src) {
-    if constexpr (sizeof(State) % 4 == 0 && alignof(State) >= 4) {
 #pragma unroll
-        for (unsigned i = 0; i < sizeof(State) / 4; ++i) ((dspb_word *)dst)[i] = ((const dspb_word *)src)[i];
-    } else {
-#pragma unroll
-        for (unsigned i = 0; i < sizeof(State); ++i) ((unsigned char *)dst)[i] = ((const unsigned char *)src)[i];
-    }
+    for (unsigned i = 0; i < kStateUnits; ++i) ((dspb_unit *)dst)[i] = ((const dspb_unit *)src)[i];
 }
-// bit-for-bit equality; every word is loaded before any is compared (no
-// short circuit: one memory round trip, not one per word)
+// bit-for-bit equality; every unit is loaded before any is compared (no
+// short circuit: one memory round trip, not one per unit)
 __device__ static bool dspb_same_state(const State *a, const State *b) {
     unsigned d = 0;
-    if constexpr (sizeof(State) % 4 == 0 && alignof(State) >= 4) {
-        const dspb_word *x = (const dspb_word *)a, *y = (const dspb_word *)b;
 #pragma unroll
-        for (unsigned i = 0; i < sizeof(State) / 4; ++i) d |= x[i] ^ y[i];
-    } else {
-        const unsigned char *x = (const unsigned char *)a, *y = (const unsigned char *)b;
-#pragma unroll
-        for (unsigned i = 0; i < sizeof(State); ++i) d |= (unsigned)(x[i] ^ y[i]);
-    }
+    for (unsigned i = 0; i < kStateUnits; ++i) d |= (unsigned)(((const dspb_unit *)a)[i] ^ ((const dspb_unit *)b)[i]);
     return d == 0;
 }
 // a split State's block-independent words from src into dst (the others stay)
@@ -164,7 +126,7 @@ __device__ static bool dspb_seg_block(const dspb_seg_args &G, unsigned long long
         // it from, and takes that State (so the walk after the boundary check
         // stops only where it meets what was rendered here)
         if (r > 0 && !dspb_same_state(&st, &G.st_blk[b])) {
-            atomicAdd(&G.stats[14], 1u);
+            atomicAdd(&G.stats[DSPB_STAT_CHAIN_RECORDS], 1u);
             dspb_copy_state((void *)&G.st_blk[b], (const void *)&st);
         }
         return true;
@@ -173,6 +135,131 @@ __device__ static bool dspb_seg_block(const dspb_seg_args &G, unsigned long long
     dspb_copy_state((void *)&G.st_blk[b], (const void *)&st);
     return true;
 }
+// ---- what pass 1 and the reruns share, however their blocks move ----------
+// (DSPB_INLINE: the callbacks' wave meets no call.)  `rerun`: a constant in
+// the kernels that are pass 1 or a rerun, G.mode in the one that is both.
+// Rounds left: the longest lane's blocks (a rerun's lanes shorten theirs).
+// s_len is typed as LDS: through a generic pointer the loads would be flat
+// until late in the compile
+typedef __attribute__((address_space(3))) unsigned dspb_lds_u;
+DSPB_INLINE unsigned dspb_seg_rounds(const dspb_lds_u *s_len, unsigned NB) {
+    unsigned rounds = 0;
+    for (unsigned i = 0; i < NB; ++i) rounds = s_len[i] > rounds ? s_len[i] : rounds;
+    return rounds;
+}
+// the State segment k starts from: the live State (segment 0, pass 1's
+// warm-ups), or the one recorded at its first block (a rerun)
+DSPB_INLINE void dspb_seg_first_state(const dspb_seg_args &G, bool rerun, unsigned k, State &st) {
+    if (k == 0xffffffffu) return;
+    dspb_copy_state((void *)&st, (rerun && (k || !G.exact)) ? (const void *)&G.st_blk[(unsigned long long)k * G.seg]
+                                                            : (const void *)G.R.S);
+    // pass 1 of a split State: the warm-up starts from the independent
+    // words the State chain recorded at its first block
+    if (!rerun && G.split && k) dspb_copy_ind_words((void *)&st, (const void *)&G.st_ind[G.level * G.K + k]);
+}
+// the State segment k ended with (a rerun that stopped early leaves the one
+// recorded before)
+DSPB_INLINE void dspb_seg_end(const dspb_seg_args &G, unsigned k, bool stopped, const State &st) {
+    if (k != 0xffffffffu && !stopped) dspb_copy_state((void *)&G.st_end[k], (const void *)&st);
+}
+// The rest of this section is shared as text: as functions, each of these
+// moved the register counts of some segment kernel (names of the kernel they
+// expand in: G, A, t, NB, C, B, SB, the s_ arrays, prm, st, stopped).
+// The gate -- pass 1 at a warm-up level that runs (it restarts the listing), a
+// rerun not to skip, a segment left for this workgroup -- then lane t's
+// segment k (~0u: none) and the s_ arrays filled
+#define DSPB_SEG_BEGIN(rerun)                                                            \
+    const unsigned base = blockIdx.x * NB;                                               \
+    if (!rerun) {                                                                        \
+        if (!dspb_seg_level_runs(G)) return;                                             \
+        if (G.level && blockIdx.x == 0 && t == 0) *G.count = 0;                          \
+    } else if (dspb_seg_skip(G)) {                                                       \
+        return;                                                                          \
+    }                                                                                    \
+    const unsigned nseg = (rerun && !G.exact) ? *(volatile unsigned *)G.count : G.K;     \
+    if (base >= nseg) return; /* the same for the whole workgroup */                     \
+    unsigned k = 0xffffffffu;                                                            \
+    if (t < NB) k = dspb_seg_lane(G, base, t, nseg, s_first, s_warm, s_len);             \
+    __syncthreads()
+// lane t's turn in round r on its block in LDS: the callback, or a rerun's stop
+#define DSPB_SEG_KEEP(RR) dspb_seg_block<RR>(G, (unsigned long long)s_first[t] + r, r, s_warm[t], st)
+#define DSPB_SEG_STEP(keep)                                             \
+    if (k != 0xffffffffu && r < s_len[t]) {                             \
+        if (keep) {                                                     \
+            float *blk = dspb_lbuf + t * SB;                            \
+            float *ptrs[CC ? CC : dspb_max_channels];                   \
+            for (unsigned c = 0; c < C; ++c) ptrs[c] = blk + c * B;     \
+            audio_callback(prm, st, ptrs, C, B, A.sr);                  \
+        } else {                                                        \
+            s_len[t] = r; /* met the recorded chain: the rest stands */ \
+            stopped = true;                                             \
+        }                                                               \
+    }
+// the channels' rows as uniform values (the channel of every access is a
+// constant, so none of them is an indexed load of the argument block), and
+// whether 16-byte accesses may be used on them
+#define DSPB_SEG_ROWS                                                                           \
+    typedef __attribute__((address_space(1))) float4 gfloat4;                                   \
+    const dspb_gfloat *xin[C];                                                                  \
+    dspb_gfloat *xout[C];                                                                       \
+    bool aligned_in = true, aligned_out = true;                                                 \
+    _Pragma("unroll") for (unsigned c = 0; c < C; ++c) {                                        \
+        xin[c] = (const dspb_gfloat *)A.in[c < A.in_ch ? c : 0];                                \
+        xout[c] = (dspb_gfloat *)A.out[c];                                                      \
+        if (c < A.in_ch) aligned_in = aligned_in && !(((unsigned long long)A.in[c]) & 15);      \
+        aligned_out = aligned_out && !(((unsigned long long)A.out[c]) & 15);                    \
+    }
+// four samples of row c at file sample gi: 16 bytes at once, or element by
+// element (zeros past EOF; an unaligned row)
+#define DSPB_SEG_LOAD4(x, c, gi)                      \
+    if (aligned_in && gi + 4 <= A.L) {                \
+        x = *(const gfloat4 *)(xin[c] + gi);          \
+    } else {                                          \
+        x.x = gi < A.L ? xin[c][gi] : 0.f;            \
+        x.y = gi + 1 < A.L ? xin[c][gi + 1] : 0.f;    \
+        x.z = gi + 2 < A.L ? xin[c][gi + 2] : 0.f;    \
+        x.w = gi + 3 < A.L ? xin[c][gi + 3] : 0.f;    \
+    }
+#define DSPB_SEG_STORE4(c, gi, o)                                                                  \
+    if (aligned_out) {                                                                             \
+        *(gfloat4 *)(xout[c] + gi) = o;                                                            \
+    } else {                                                                                       \
+        xout[c][gi] = o.x, xout[c][gi + 1] = o.y, xout[c][gi + 2] = o.z, xout[c][gi + 3] = o.w;    \
+    }
+// diagnostics (a module compiled with DSPB_SEG_TIMING set, module.cpp): where
+// wave 0's lane 0 spends pass 1's rounds, in shader clocks / 16 per phase,
+// summed over the workgroups into stats (dsp_module_seg_timing).  Phases of
+// dspb_segments_pf: 0 staging + barrier, 1 next round's loads issued, 2 the
+// callbacks, 3 the barrier after them, 4 copy-out + barrier; of
+// dspb_segments_roles: 0 the first round staged, 2 the callbacks, 3 the
+// barrier after them, 4 take / put + barrier (1 unused)
+struct dspb_seg_timer {
+#ifdef DSPB_SEG_TIMING
+    unsigned long long tm[5] = {0, 0, 0, 0, 0}, t0, nr = 0;
+    bool on;
+    DSPB_INLINE_MEMBER explicit dspb_seg_timer(bool rerun)
+        : t0(__builtin_amdgcn_s_memtime()), on(!rerun && threadIdx.x == 0) {}
+    DSPB_INLINE_MEMBER void mark(unsigned i) {
+        if (!on) return;
+        const unsigned long long tn = __builtin_amdgcn_s_memtime();
+        tm[i] += tn - t0;
+        t0 = tn;
+    }
+    DSPB_INLINE_MEMBER void round() { ++nr; }
+    DSPB_INLINE_MEMBER void flush(const dspb_seg_args &G) {
+        if (!on) return;
+        for (int i = 0; i < 5; ++i) atomicAdd(&G.stats[DSPB_STAT_TIMING + i], (unsigned)(tm[i] >> 4));
+        atomicAdd(&G.stats[DSPB_STAT_TIMING_WGS], 1u);
+        atomicAdd(&G.stats[DSPB_STAT_TIMING_ROUNDS], (unsigned)nr);
+    }
+#else
+    DSPB_INLINE_MEMBER explicit dspb_seg_timer(bool) {}
+    DSPB_INLINE_MEMBER void mark(unsigned) {}
+    DSPB_INLINE_MEMBER void round() {}
+    DSPB_INLINE_MEMBER void flush(const dspb_seg_args &) {}
+#endif
+};
+#define DSPB_TMARK(i) timer.mark(i);
 // pass 1 / rerun, any shape: lane t of wave 0 runs segment k_t, rounds of one
 // block per lane staged in LDS by all 256 threads (render_audio's copy: zeros
 // past EOF and for the channels the file lacks), kept blocks copied out after
@@ -184,34 +271,16 @@ __device__ static void dspb_segments(const dspb_seg_args &G) {
     const dspb_render_args &A = G.R;
     const unsigned C = CC ? CC : A.C, B = BB ? BB : A.B, CB = C * B, NB = A.lds_nb, SB = A.lds_stride;
     const unsigned t = threadIdx.x, nt = blockDim.x;
-    const unsigned base = blockIdx.x * NB;
-    if (!G.mode) {  // pass 1: at a warm-up level that runs; it restarts the listing
-        if (!dspb_seg_level_runs(G)) return;
-        if (G.level && blockIdx.x == 0 && t == 0) *G.count = 0;
-    } else if (dspb_seg_skip(G)) {
-        return;
-    }
-    const unsigned nseg = (G.mode && !G.exact) ? *(volatile unsigned *)G.count : G.K;
-    if (base >= nseg) return;  // the same for the whole workgroup
-    unsigned k = 0xffffffffu;
-    if (t < NB) k = dspb_seg_lane(G, base, t, nseg, s_first, s_warm, s_len);
-    __syncthreads();
-    unsigned rounds = 0;
-    for (unsigned i = 0; i < NB; ++i) rounds = s_len[i] > rounds ? s_len[i] : rounds;
+    DSPB_SEG_BEGIN(G.mode);
+    unsigned rounds = dspb_seg_rounds((const dspb_lds_u *)s_len, NB);
     Parameters prm = dspb_from_global<Parameters>(A.P);
     State st;
     bool stopped = false;
-    if (k != 0xffffffffu) {
-        dspb_copy_state((void *)&st, (G.mode && (k || !G.exact)) ? (const void *)&G.st_blk[(unsigned long long)k * G.seg]
-                                                                 : (const void *)A.S);
-        // pass 1 of a split State: the warm-up starts from the independent
-        // words the State chain recorded at its first block
-        if (!G.mode && G.split && k) dspb_copy_ind_words((void *)&st, (const void *)&G.st_ind[G.level * G.K + k]);
-    }
+    dspb_seg_first_state(G, G.mode != 0, k, st);
     // the channels' rows in LDS (an access by a lane-dependent channel reads
     // them there, not from the argument block in memory)
-    __shared__ const float *s_in[16];
-    __shared__ float *s_out[16];
+    __shared__ const float *s_in[dspb_max_channels];
+    __shared__ float *s_out[dspb_max_channels];
     if (t < C) {
         s_in[t] = t < A.in_ch ? A.in[t] : nullptr;
         s_out[t] = A.out[t];
@@ -242,18 +311,7 @@ __device__ static void dspb_segments(const dspb_seg_args &G) {
                 if (dst[u] != 0xffffffffu) dspb_lbuf[dst[u]] = v[u];
         }
         __syncthreads();
-        if (k != 0xffffffffu && r < s_len[t]) {
-            if (G.mode ? dspb_seg_block<true>(G, (unsigned long long)s_first[t] + r, r, s_warm[t], st)
-                       : dspb_seg_block<false>(G, (unsigned long long)s_first[t] + r, r, s_warm[t], st)) {
-                float *blk = dspb_lbuf + t * SB;
-                float *ptrs[CC ? CC : 16];
-                for (unsigned c = 0; c < C; ++c) ptrs[c] = blk + c * B;
-                audio_callback(prm, st, ptrs, C, B, A.sr);
-            } else {
-                s_len[t] = r;  // met the recorded chain: the rest stands
-                stopped = true;
-            }
-        }
+        DSPB_SEG_STEP(G.mode ? DSPB_SEG_KEEP(true) : DSPB_SEG_KEEP(false))
         __syncthreads();
         for (unsigned j = t; j < NE; j += nt) {
             const unsigned i = j / CB, e = j - i * CB, c = e / B, s = e - c * B;
@@ -261,10 +319,9 @@ __device__ static void dspb_segments(const dspb_seg_args &G) {
                 ((dspb_gfloat *)s_out[c])[(unsigned long long)(s_first[i] + r) * B + s] = dspb_lbuf[i * SB + e];
         }
         __syncthreads();
-        rounds = 0;
-        for (unsigned i = 0; i < NB; ++i) rounds = s_len[i] > rounds ? s_len[i] : rounds;
+        rounds = dspb_seg_rounds((const dspb_lds_u *)s_len, NB);
     }
-    if (k != 0xffffffffu && !stopped) dspb_copy_state((void *)&G.st_end[k], (const void *)&st);
+    dspb_seg_end(G, k, stopped, st);
 }
 // the same for a constant channel count and 4 | B, software pipelined: round
 // r + 1's blocks are in flight into registers (16-byte loads, all issued at
@@ -276,54 +333,23 @@ template <unsigned CC, unsigned BB, bool kRerun>
 __device__ static void dspb_segments_pf(const dspb_seg_args &G) {
     extern __shared__ float dspb_lbuf[];
     __shared__ unsigned s_first[64], s_warm[64], s_len[64];
-    constexpr unsigned C = CC;
-    const unsigned B = BB ? BB : G.R.B, CB = C * B, SB = CB + 2u, NB = BB ? dspb_seg_nb(CC * BB + 2u) : G.R.lds_nb;
+    constexpr unsigned C = CC, NBC = BB ? dspb_seg_nb(dspb_stride_pf(CC, BB)) : 0u;  // (a constant B's lanes)
+    const unsigned B = BB ? BB : G.R.B, SB = (unsigned)dspb_stride_pf(C, B), NB = BB ? NBC : G.R.lds_nb;
     // per channel: NB rows of B / 4 float4, at most PV of them per thread
     // (a round holds fewer than DSPB_LDS_ROUND_BYTES / (16 C) float4 per channel)
     const unsigned R4 = B / 4u, T4 = NB * R4;
-    constexpr unsigned PV = BB ? (dspb_seg_nb(CC * BB + 2u) * (BB / 4u) + 255u) / 256u
-                               : (DSPB_LDS_ROUND_BYTES / (16u * CC) + 255u) / 256u;
-    constexpr bool kFull = BB && (dspb_seg_nb(CC * BB + 2u) * (BB / 4u)) % 256u == 0;
-    static_assert(!BB || (dspb_seg_nb(CC * BB + 2u) <= 64 && BB % 4 == 0), "one wave runs a round's callbacks");
-    typedef __attribute__((address_space(1))) float4 gfloat4;
+    constexpr unsigned PV = BB ? (NBC * (BB / 4u) + 255u) / 256u : (DSPB_LDS_ROUND_BYTES / (16u * CC) + 255u) / 256u;
+    constexpr bool kFull = BB && (NBC * (BB / 4u)) % 256u == 0;
+    static_assert(!BB || (NBC <= 64 && BB % 4 == 0), "one wave runs a round's callbacks");
     const dspb_render_args &A = G.R;
     const unsigned t = threadIdx.x;
-    const unsigned base = blockIdx.x * NB;
-    if (!kRerun) {  // pass 1: at a warm-up level that runs; it restarts the listing
-        if (!dspb_seg_level_runs(G)) return;
-        if (G.level && blockIdx.x == 0 && t == 0) *G.count = 0;
-    } else if (dspb_seg_skip(G)) {
-        return;
-    }
-    const unsigned nseg = (kRerun && !G.exact) ? *(volatile unsigned *)G.count : G.K;
-    if (base >= nseg) return;  // the same for the whole workgroup
-    unsigned k = 0xffffffffu;
-    if (t < NB) k = dspb_seg_lane(G, base, t, nseg, s_first, s_warm, s_len);
-    __syncthreads();
-    unsigned rounds = 0;
-    for (unsigned i = 0; i < NB; ++i) rounds = s_len[i] > rounds ? s_len[i] : rounds;
-    // the channels' rows as uniform values (the channel of every access below
-    // is a constant, so none of them is an indexed load of the argument block)
-    const dspb_gfloat *xin[C];
-    dspb_gfloat *xout[C];
-    bool aligned_in = true, aligned_out = true;
-#pragma unroll
-    for (unsigned c = 0; c < C; ++c) {
-        xin[c] = (const dspb_gfloat *)A.in[c < A.in_ch ? c : 0];
-        xout[c] = (dspb_gfloat *)A.out[c];
-        if (c < A.in_ch) aligned_in = aligned_in && !(((unsigned long long)A.in[c]) & 15);
-        aligned_out = aligned_out && !(((unsigned long long)A.out[c]) & 15);
-    }
+    DSPB_SEG_BEGIN(kRerun);
+    unsigned rounds = dspb_seg_rounds((const dspb_lds_u *)s_len, NB);
+    DSPB_SEG_ROWS
     Parameters prm = dspb_from_global<Parameters>(A.P);
     State st;
     bool stopped = false;
-    if (k != 0xffffffffu) {
-        dspb_copy_state((void *)&st, (kRerun && (k || !G.exact)) ? (const void *)&G.st_blk[(unsigned long long)k * G.seg]
-                                                                  : (const void *)A.S);
-        // pass 1 of a split State: the warm-up starts from the independent
-        // words the State chain recorded at its first block
-        if (!kRerun && G.split && k) dspb_copy_ind_words((void *)&st, (const void *)&G.st_ind[G.level * G.K + k]);
-    }
+    dspb_seg_first_state(G, kRerun, k, st);
     // a constant B prefetches a whole round (PB = PV) while the callbacks run;
     // a runtime B stages in batches of 4 float4 per channel at the round's
     // start (a whole round's registers would spill)
@@ -338,14 +364,7 @@ __device__ static void dspb_segments_pf(const dspb_seg_args &G) {
                 float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
                 if ((kFull || q < T4) && r < s_len[i] && c < A.in_ch) {
                     const unsigned long long gi = (unsigned long long)(s_first[i] + r) * B + s;
-                    if (aligned_in && gi + 4 <= A.L) {
-                        x = *(const gfloat4 *)(xin[c] + gi);
-                    } else {
-                        x.x = gi < A.L ? xin[c][gi] : 0.f;
-                        x.y = gi + 1 < A.L ? xin[c][gi + 1] : 0.f;
-                        x.z = gi + 2 < A.L ? xin[c][gi + 2] : 0.f;
-                        x.w = gi + 3 < A.L ? xin[c][gi + 3] : 0.f;
-                    }
+                    DSPB_SEG_LOAD4(x, c, gi)
                 }
                 pf[c][v] = x;
             }
@@ -357,28 +376,11 @@ __device__ static void dspb_segments_pf(const dspb_seg_args &G) {
 #pragma unroll
             for (unsigned v = 0; v < PB; ++v) {
                 const unsigned q = t + 256u * (v0 + v), i = q / R4, s = (q - i * R4) * 4u;
-                if ((kFull || q < T4) && r < s_len[i]) {
-                    float2 *d = (float2 *)(dspb_lbuf + i * SB + c * B + s);
-                    d[0] = make_float2(pf[c][v].x, pf[c][v].y);
-                    d[1] = make_float2(pf[c][v].z, pf[c][v].w);
-                }
+                if ((kFull || q < T4) && r < s_len[i]) dspb_lds_put4(dspb_lbuf + i * SB + c * B + s, pf[c][v]);
             }
         }
     };
-#ifdef DSPB_SEG_TIMING
-    // diagnostics (a module compiled with DSPB_SEG_TIMING set, module.cpp):
-    // where wave 0's lane 0 spends pass 1's rounds, in shader clocks, summed
-    // over the workgroups into stats[16, 24) (dsp_module_seg_timing)
-    unsigned long long tm[5] = {0, 0, 0, 0, 0}, t0 = __builtin_amdgcn_s_memtime(), nr = 0;
-#define DSPB_TMARK(i)                                                   \
-    if (!kRerun && t == 0) {                                            \
-        const unsigned long long tn = __builtin_amdgcn_s_memtime();     \
-        tm[i] += tn - t0;                                               \
-        t0 = tn;                                                        \
-    }
-#else
-#define DSPB_TMARK(i)
-#endif
+    dspb_seg_timer timer(kRerun);
     if (BB && rounds) load(0, 0);
     for (unsigned r = 0; r < rounds; ++r) {
         if constexpr (BB != 0) {
@@ -393,17 +395,7 @@ __device__ static void dspb_segments_pf(const dspb_seg_args &G) {
         DSPB_TMARK(0)
         if (BB && r + 1 < rounds) load(r + 1, 0);  // in flight while the callbacks run
         DSPB_TMARK(1)
-        if (k != 0xffffffffu && r < s_len[t]) {
-            if (dspb_seg_block<kRerun>(G, (unsigned long long)s_first[t] + r, r, s_warm[t], st)) {
-                float *blk = dspb_lbuf + t * SB;
-                float *ptrs[C];
-                for (unsigned c = 0; c < C; ++c) ptrs[c] = blk + c * B;
-                audio_callback(prm, st, ptrs, C, B, A.sr);
-            } else {
-                s_len[t] = r;  // met the recorded chain: the rest stands
-                stopped = true;
-            }
-        }
+        DSPB_SEG_STEP(DSPB_SEG_KEEP(kRerun))
         DSPB_TMARK(2)
         __syncthreads();
         DSPB_TMARK(3)
@@ -414,35 +406,18 @@ __device__ static void dspb_segments_pf(const dspb_seg_args &G) {
                 const unsigned q = t + 256u * v, i = q / R4, s = (q - i * R4) * 4u;
                 if ((kFull || q < T4) && r >= s_warm[i] && r < s_len[i]) {
                     const unsigned long long gi = (unsigned long long)(s_first[i] + r) * B + s;
-                    const float2 *d = (const float2 *)(dspb_lbuf + i * SB + c * B + s);
-                    const float2 lo = d[0], hi = d[1];
-                    if (aligned_out) {
-                        *(gfloat4 *)(xout[c] + gi) = make_float4(lo.x, lo.y, hi.x, hi.y);
-                    } else {
-                        xout[c][gi] = lo.x, xout[c][gi + 1] = lo.y, xout[c][gi + 2] = hi.x, xout[c][gi + 3] = hi.y;
-                    }
+                    const float4 o = dspb_lds_get4(dspb_lbuf + i * SB + c * B + s);
+                    DSPB_SEG_STORE4(c, gi, o)
                 }
             }
         }
         __syncthreads();
-        rounds = 0;
-        for (unsigned i = 0; i < NB; ++i) rounds = s_len[i] > rounds ? s_len[i] : rounds;
+        rounds = dspb_seg_rounds((const dspb_lds_u *)s_len, NB);
         DSPB_TMARK(4)
-#ifdef DSPB_SEG_TIMING
-        ++nr;
-#endif
+        timer.round();
     }
-    if (k != 0xffffffffu && !stopped) dspb_copy_state((void *)&G.st_end[k], (const void *)&st);
-#ifdef DSPB_SEG_TIMING
-    if (!kRerun && t == 0) {
-        // (phases: 0 staging + barrier, 1 next round's loads issued, 2 the
-        // callbacks, 3 the barrier after them, 4 copy-out + barrier)
-        for (int i = 0; i < 5; ++i) atomicAdd(&G.stats[16 + i], (unsigned)(tm[i] >> 4));
-        atomicAdd(&G.stats[21], 1u);
-        atomicAdd(&G.stats[22], (unsigned)nr);
-    }
-#endif
-#undef DSPB_TMARK
+    dspb_seg_end(G, k, stopped, st);
+    timer.flush(G);
 }
 // the same for a constant B, with the work split by role: wave 0 runs the
 // callbacks and nothing else; waves 1-3 move the blocks.  A round's kept
@@ -459,7 +434,7 @@ template <unsigned CC, unsigned BB, bool kRerun>
 __device__ __attribute__((always_inline, flatten)) static void dspb_segments_roles(const dspb_seg_args &G) {
     extern __shared__ float dspb_lbuf[];
     __shared__ unsigned s_first[64], s_warm[64], s_len[64];
-    constexpr unsigned C = CC, B = BB, SB = C * B + 2u, NB = dspb_seg_nb(CC * BB + 2u);
+    constexpr unsigned C = CC, B = BB, SB = dspb_stride_pf(C, B), NB = dspb_seg_nb(SB);
     // the movers (waves 1-3) move float4 units: one 16-byte load / store per
     // unit in HBM, two 8-byte LDS accesses (rows are 8-byte aligned: C B + 2
     // floats apart, so that the callback lanes sit on distinct banks).
@@ -472,30 +447,9 @@ __device__ __attribute__((always_inline, flatten)) static void dspb_segments_rol
     static_assert(NB <= 64 && BB % 4 == 0, "one wave runs a round's callbacks");
     const dspb_render_args &A = G.R;
     const unsigned t = threadIdx.x;
-    const unsigned base = blockIdx.x * NB;
-    if (!kRerun) {  // pass 1: at a warm-up level that runs; it restarts the listing
-        if (!dspb_seg_level_runs(G)) return;
-        if (G.level && blockIdx.x == 0 && t == 0) *G.count = 0;
-    } else if (dspb_seg_skip(G)) {
-        return;
-    }
-    const unsigned nseg = (kRerun && !G.exact) ? *(volatile unsigned *)G.count : G.K;
-    if (base >= nseg) return;  // the same for the whole workgroup
-    unsigned k = 0xffffffffu;
-    if (t < NB) k = dspb_seg_lane(G, base, t, nseg, s_first, s_warm, s_len);
-    __syncthreads();
-    unsigned rounds = 0;
-    for (unsigned i = 0; i < NB; ++i) rounds = s_len[i] > rounds ? s_len[i] : rounds;
-    const dspb_gfloat *xin[C];
-    dspb_gfloat *xout[C];
-    bool aligned_in = true, aligned_out = true;
-#pragma unroll
-    for (unsigned c = 0; c < C; ++c) {
-        xin[c] = (const dspb_gfloat *)A.in[c < A.in_ch ? c : 0];
-        xout[c] = (dspb_gfloat *)A.out[c];
-        if (c < A.in_ch) aligned_in = aligned_in && !(((unsigned long long)A.in[c]) & 15);
-        aligned_out = aligned_out && !(((unsigned long long)A.out[c]) & 15);
-    }
+    DSPB_SEG_BEGIN(kRerun);
+    unsigned rounds = dspb_seg_rounds((const dspb_lds_u *)s_len, NB);
+    DSPB_SEG_ROWS
     const bool mover = t >= 64u;
     // (movers only; made opaque once per round, so that the slots' indices
     // are recomputed where used instead of 24 of them held in registers
@@ -523,7 +477,6 @@ __device__ __attribute__((always_inline, flatten)) static void dspb_segments_rol
     auto len_of = [&](unsigned i) { return (unsigned)__builtin_amdgcn_readlane((int)m_len, (int)i); };
     auto warm_of = [&](unsigned i) { return (unsigned)__builtin_amdgcn_readlane((int)m_warm, (int)i); };
     auto first_of = [&](unsigned i) { return (unsigned)__builtin_amdgcn_readlane((int)m_first, (int)i); };
-    typedef __attribute__((address_space(1))) float4 gfloat4;
     float4 pf[C][PV], ob[C][PV];
     auto load = [&](unsigned r) {
 #pragma unroll
@@ -534,14 +487,7 @@ __device__ __attribute__((always_inline, flatten)) static void dspb_segments_rol
                 float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (slot(v, i, s) && r < len_of(i) && c < A.in_ch) {
                     const unsigned long long gi = (unsigned long long)(first_of(i) + r) * B + s;
-                    if (aligned_in && gi + 4 <= A.L) {
-                        x = *(const gfloat4 *)(xin[c] + gi);
-                    } else {
-                        x.x = gi < A.L ? xin[c][gi] : 0.f;
-                        x.y = gi + 1 < A.L ? xin[c][gi + 1] : 0.f;
-                        x.z = gi + 2 < A.L ? xin[c][gi + 2] : 0.f;
-                        x.w = gi + 3 < A.L ? xin[c][gi + 3] : 0.f;
-                    }
+                    DSPB_SEG_LOAD4(x, c, gi)
                 }
                 pf[c][v] = x;
             }
@@ -552,11 +498,7 @@ __device__ __attribute__((always_inline, flatten)) static void dspb_segments_rol
 #pragma unroll
             for (unsigned v = 0; v < PV; ++v) {
                 unsigned i, s;
-                if (slot(v, i, s) && r < len_of(i)) {
-                    float2 *d = (float2 *)(dspb_lbuf + i * SB + c * B + s);
-                    d[0] = make_float2(pf[c][v].x, pf[c][v].y);
-                    d[1] = make_float2(pf[c][v].z, pf[c][v].w);
-                }
+                if (slot(v, i, s) && r < len_of(i)) dspb_lds_put4(dspb_lbuf + i * SB + c * B + s, pf[c][v]);
             }
     };
     // round r's kept blocks out of their slots, round r + 1's in (put: r + 1
@@ -569,15 +511,9 @@ __device__ __attribute__((always_inline, flatten)) static void dspb_segments_rol
             for (unsigned v = 0; v < PV; ++v) {
                 unsigned i, s;
                 const bool in = slot(v, i, s);
-                float2 *d = (float2 *)(dspb_lbuf + i * SB + c * B + s);
-                if (in && r >= warm_of(i) && r < len_of(i)) {
-                    const float2 lo = d[0], hi = d[1];
-                    ob[c][v] = make_float4(lo.x, lo.y, hi.x, hi.y);
-                }
-                if (in && put_next && r + 1 < len_of(i)) {
-                    d[0] = make_float2(pf[c][v].x, pf[c][v].y);
-                    d[1] = make_float2(pf[c][v].z, pf[c][v].w);
-                }
+                float *d = dspb_lbuf + i * SB + c * B + s;
+                if (in && r >= warm_of(i) && r < len_of(i)) ob[c][v] = dspb_lds_get4(d);
+                if (in && put_next && r + 1 < len_of(i)) dspb_lds_put4(d, pf[c][v]);
             }
     };
     auto send = [&](unsigned r) {
@@ -589,33 +525,15 @@ __device__ __attribute__((always_inline, flatten)) static void dspb_segments_rol
                 if (slot(v, i, s) && r >= warm_of(i) && r < len_of(i)) {
                     const unsigned long long gi = (unsigned long long)(first_of(i) + r) * B + s;
                     const float4 o = ob[c][v];
-                    if (aligned_out) {
-                        *(gfloat4 *)(xout[c] + gi) = o;
-                    } else {
-                        xout[c][gi] = o.x, xout[c][gi + 1] = o.y, xout[c][gi + 2] = o.z, xout[c][gi + 3] = o.w;
-                    }
+                    DSPB_SEG_STORE4(c, gi, o)
                 }
             }
     };
     Parameters prm = dspb_from_global<Parameters>(A.P);
     State st;
     bool stopped = false;
-    if (k != 0xffffffffu) {
-        dspb_copy_state((void *)&st, (kRerun && (k || !G.exact)) ? (const void *)&G.st_blk[(unsigned long long)k * G.seg]
-                                                                  : (const void *)A.S);
-        if (!kRerun && G.split && k) dspb_copy_ind_words((void *)&st, (const void *)&G.st_ind[G.level * G.K + k]);
-    }
-#ifdef DSPB_SEG_TIMING
-    unsigned long long tmk[5] = {0, 0, 0, 0, 0}, t0 = __builtin_amdgcn_s_memtime(), nr = 0;
-#define DSPB_TMARK(i)                                                   \
-    if (!kRerun && t == 0) {                                            \
-        const unsigned long long tn = __builtin_amdgcn_s_memtime();     \
-        tmk[i] += tn - t0;                                              \
-        t0 = tn;                                                        \
-    }
-#else
-#define DSPB_TMARK(i)
-#endif
+    dspb_seg_first_state(G, kRerun, k, st);
+    dspb_seg_timer timer(kRerun);
     if (mover && rounds) {
         refresh();
         load(0);
@@ -630,29 +548,16 @@ __device__ __attribute__((always_inline, flatten)) static void dspb_segments_rol
     // not live across the callbacks' code, which has the registers to itself
     if (__builtin_amdgcn_readfirstlane(t >> 6) == 0) {
         for (unsigned r = 0; r < rounds;) {
-            if (k != 0xffffffffu && r < s_len[t]) {
-                if (dspb_seg_block<kRerun>(G, (unsigned long long)s_first[t] + r, r, s_warm[t], st)) {
-                    float *blk = dspb_lbuf + t * SB;
-                    float *ptrs[C];
-                    for (unsigned c = 0; c < C; ++c) ptrs[c] = blk + c * B;
-                    audio_callback(prm, st, ptrs, C, B, A.sr);
-                } else {
-                    s_len[t] = r;  // met the recorded chain: the rest stands
-                    stopped = true;
-                }
-            }
+            DSPB_SEG_STEP(DSPB_SEG_KEEP(kRerun))
             DSPB_TMARK(2)
             __syncthreads();  // (A) the callbacks of round r are done, s_len final for it
             DSPB_TMARK(3)
-            unsigned next = 0;
-            for (unsigned i = 0; i < NB; ++i) next = s_len[i] > next ? s_len[i] : next;
+            const unsigned next = dspb_seg_rounds((const dspb_lds_u *)s_len, NB);
             __syncthreads();  // (B) round r + 1 staged by the movers
             DSPB_TMARK(4)
             rounds = next;
             ++r;
-#ifdef DSPB_SEG_TIMING
-            ++nr;
-#endif
+            timer.round();
         }
     } else {
         for (unsigned r = 0; r < rounds;) {
@@ -675,17 +580,8 @@ __device__ __attribute__((always_inline, flatten)) static void dspb_segments_rol
             ++r;
         }
     }
-    if (k != 0xffffffffu && !stopped) dspb_copy_state((void *)&G.st_end[k], (const void *)&st);
-#ifdef DSPB_SEG_TIMING
-    if (!kRerun && t == 0) {
-        // (phases: 0 the first round staged, 2 the callbacks, 3 the barrier
-        // after them, 4 take / put + barrier; 1 unused)
-        for (int i = 0; i < 5; ++i) atomicAdd(&G.stats[16 + i], (unsigned)(tmk[i] >> 4));
-        atomicAdd(&G.stats[21], 1u);
-        atomicAdd(&G.stats[22], (unsigned)nr);
-    }
-#endif
-#undef DSPB_TMARK
+    dspb_seg_end(G, k, stopped, st);
+    timer.flush(G);
 }
 #define DSPB_SEG_KERNEL(name, CC, BB)                                                \
     extern "C" __global__ __launch_bounds__(256) void name(dspb_seg_args G) { dspb_segments<CC, BB>(G); }
@@ -704,17 +600,16 @@ __device__ __attribute__((always_inline, flatten)) static void dspb_segments_rol
 #define DSPB_SEG_ROLES_KERNEL(name, CC, BB, RR)                                        \
     extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RR ? 1 : 2, 2))) void name(  \
         dspb_seg_args G) { dspb_segments_roles<CC, BB, RR>(G); }
-DSPB_SEG_ROLES_KERNEL(dspb_seg_c2b512, 2, 512, false)
-// (the reruns keep the single-role kernel: the roles' unrolled movers leave
-// the rerun's State comparison no registers, and their arrays go to scratch)
-DSPB_SEG_PF_KERNEL(dspb_seg_c2b512_rerun, 2, 512, true)
-DSPB_SEG_PF_KERNEL(dspb_seg_c2, 2, 0, false)
-DSPB_SEG_PF_KERNEL(dspb_seg_c2_rerun, 2, 0, true)
-DSPB_SEG_PF_KERNEL(dspb_seg_c1, 1, 0, false)
-DSPB_SEG_PF_KERNEL(dspb_seg_c1_rerun, 1, 0, true)
-DSPB_SEG_PF_KERNEL(dspb_seg_c4, 4, 0, false)
-DSPB_SEG_PF_KERNEL(dspb_seg_c4_rerun, 4, 0, true)
-DSPB_SEG_KERNEL(dspb_seg, 0, 0)
+// (dspb_seg_c2b512's reruns keep the single-role kernel: the roles' unrolled
+// movers leave the rerun's State comparison no registers, and their arrays
+// go to scratch)
+#define DSPB_SEG_KERNEL_roles(name, CC, BB, RR) DSPB_SEG_ROLES_KERNEL(name, CC, BB, RR)
+#define DSPB_SEG_KERNEL_pf(name, CC, BB, RR) DSPB_SEG_PF_KERNEL(name, CC, BB, RR)
+#define DSPB_SEG_KERNEL_any(name, CC, BB, RR) DSPB_SEG_KERNEL(name, CC, BB)
+#define DSPB_SEG_KERNEL_same(name, CC, BB, RR)
+#define DSPB_SEG_KERNEL_PAIR(name, CC, BB, P1, RR) \
+    DSPB_SEG_KERNEL_##P1(name, CC, BB, false) DSPB_SEG_KERNEL_##RR(name##_rerun, CC, BB, true)
+DSPB_SEG_KERNELS(DSPB_SEG_KERNEL_PAIR)
 // segment k (k >= 1) rendered its first block from st_blk[k seg]; the true
 // State there is st_end[k - 1] if segment k - 1 is exact: flag the segments
 // where the two differ and, when a rerun follows, list them and give each
@@ -727,9 +622,9 @@ extern "C" __global__ void dspb_seg_check(dspb_seg_args G) {
         // after the State chain's exact rerun: every boundary, the chain's
         // record of a segment's first State against the State the segment
         // before ended with (the chain is checked, not trusted)
-    } else if (G.level != 0xffffffffu) {  // pass 1's check: where pass 1 ran
+    } else if (G.level != DSPB_NO_LEVEL) {  // pass 1's check: where pass 1 ran
         if (!dspb_seg_level_runs(G)) return;
-        if (blockIdx.x == 0 && threadIdx.x == 0) G.stats[8 + G.level] = 1;
+        if (blockIdx.x == 0 && threadIdx.x == 0) G.stats[DSPB_STAT_LEVEL_RAN + G.level] = 1;
     } else if (*(volatile unsigned *)G.prev_count == 0) {
         return;  // the rerun before rendered nothing: the flags stand
     }
@@ -743,24 +638,14 @@ extern "C" __global__ void dspb_seg_check(dspb_seg_args G) {
     State *first = &G.st_blk[(unsigned long long)k * G.seg];
     const State *prev = &G.st_end[k - 1];
     bool diff = false;
-    constexpr bool kWords = sizeof(State) % 4 == 0 && alignof(State) >= 4;
-    constexpr unsigned n = kWords ? sizeof(State) / 4 : sizeof(State);
-    if constexpr (kWords) {
-        for (unsigned i = lane; i < n; i += 64) diff = diff || ((const dspb_word *)first)[i] != ((const dspb_word *)prev)[i];
-    } else {
-        for (unsigned i = lane; i < n; i += 64)
-            diff = diff || ((const unsigned char *)first)[i] != ((const unsigned char *)prev)[i];
-    }
+    for (unsigned i = lane; i < kStateUnits; i += 64)
+        diff = diff || ((const dspb_unit *)first)[i] != ((const dspb_unit *)prev)[i];
     const bool any = __any(diff) != 0;
     if (lane == 0) G.flags[k] = any ? 1 : 0;
     if (!any) return;
     if (lane == 0) atomicAdd(&G.stats[G.pass], 1u);
     if (G.mode) {
-        if constexpr (kWords) {
-            for (unsigned i = lane; i < n; i += 64) ((dspb_word *)first)[i] = ((const dspb_word *)prev)[i];
-        } else {
-            for (unsigned i = lane; i < n; i += 64) ((unsigned char *)first)[i] = ((const unsigned char *)prev)[i];
-        }
+        for (unsigned i = lane; i < kStateUnits; i += 64) ((dspb_unit *)first)[i] = ((const dspb_unit *)prev)[i];
         if (lane == 0) G.list[atomicAdd(G.count, 1u)] = k;
     }
 }
@@ -832,7 +717,7 @@ __device__ static void dspb_seg_walk(const dspb_seg_args &G) {
                     break;
                 }
                 if (t == 0) {
-                    float *ptrs[CC ? CC : 16];
+                    float *ptrs[CC ? CC : dspb_max_channels];
                     for (unsigned c = 0; c < C; ++c) ptrs[c] = cur + c * B;
                     audio_callback(prm, local, ptrs, C, B, A.sr);
                 } else if (t >= 64) {
@@ -852,7 +737,7 @@ __device__ static void dspb_seg_walk(const dspb_seg_args &G) {
         }
     }
     __syncthreads();
-    if (t == 0) G.stats[7] = reruns;
+    if (t == 0) G.stats[DSPB_STAT_WALK_RERUNS] = reruns;
     // the live State: the last segment's final State (s_prev when the walk
     // rendered it to its end, else st_end as pass 1 / a rerun left it)
     const unsigned char *last = prev_ended ? (const unsigned char *)s_prev
@@ -861,8 +746,7 @@ __device__ static void dspb_seg_walk(const dspb_seg_args &G) {
 }
 #define DSPB_WALK_KERNEL(name, CC, BB)                                                 \
     extern "C" __global__ __launch_bounds__(256) void name(dspb_seg_args G) { dspb_seg_walk<CC, BB>(G); }
-DSPB_WALK_KERNEL(dspb_seg_walk_c2b512, 2, 512)
-DSPB_WALK_KERNEL(dspb_seg_walk_any, 0, 0)
+DSPB_WALK_KERNELS(DSPB_WALK_KERNEL)
 
 // ---- a State that never forgets (module_render_seg, chain) -----------------
 // An oscillator's phase never forgets where it started: no warm-up level
@@ -875,16 +759,16 @@ DSPB_WALK_KERNEL(dspb_seg_walk_any, 0, 0)
 // cosine).  The exact rerun (G.exact) then renders every segment from its
 // recorded first State, in parallel -- the serial chain's bits.  The host
 // takes a chain kernel only when its private memory is smaller than the block
-// (module.cpp kChainShapes): a block the State depends on stays in scratch,
+// (module.cpp chain_kernel): a block the State depends on stays in scratch,
 // and such a callback renders serially as before.  Within a speculative
 // render (G.mode 2) the chain runs only when the last warm-up level tried
 // failed (dspb_seg_level_runs on the level after it), and says so in
-// stats[12]: the reruns and the walk then return at once, and the exact
+// DSPB_STAT_CHAINED: the reruns and the walk then return at once, and the exact
 // rerun (G.exact 2) renders the segments.  The chain is checked, not trusted:
 // the exact rerun compares every block's record with the State it renders the
 // block from, a check compares every segment's first State with the State the
 // segment before ended with, and the walk renders serially from the true
-// State whatever differs (stats[13], [14]: the host then stops taking the
+// State whatever differs (DSPB_STAT_CHAIN_MISMATCH / _RECORDS: the host then stops taking the
 // chain for these Parameters).
 template <unsigned CC, unsigned BB>
 __device__ static void dspb_seg_chain(const dspb_seg_args &G) {
@@ -892,9 +776,9 @@ __device__ static void dspb_seg_chain(const dspb_seg_args &G) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     if (G.mode == 2) {
         if (!dspb_seg_level_runs(G)) return;
-        G.stats[12] = 1u;
+        G.stats[DSPB_STAT_CHAINED] = 1u;
     }
-    constexpr unsigned BMAX = BB ? BB : 4096u;
+    constexpr unsigned BMAX = BB ? BB : dspb_chain_max_b;
     const unsigned B = BB ? BB : A.B;
     const Parameters prm = dspb_from_global<Parameters>(A.P);
     State st;
@@ -926,10 +810,7 @@ __device__ static void dspb_seg_chain(const dspb_seg_args &G) {
 }
 #define DSPB_CHAIN_KERNEL(name, CC, BB)                                                \
     extern "C" __global__ __launch_bounds__(64) void name(dspb_seg_args G) { dspb_seg_chain<CC, BB>(G); }
-DSPB_CHAIN_KERNEL(dspb_seg_chain_c2b512, 2, 512)
-DSPB_CHAIN_KERNEL(dspb_seg_chain_c2, 2, 0)
-DSPB_CHAIN_KERNEL(dspb_seg_chain_c1, 1, 0)
-DSPB_CHAIN_KERNEL(dspb_seg_chain_c4, 4, 0)
+DSPB_CHAIN_KERNELS(DSPB_CHAIN_KERNEL)
 
 // ---- a split State: the chain of its block-independent words --------------
 // The callback in file order, as dspb_seg_chain (over 64 lanes' ranges of
@@ -944,7 +825,7 @@ __device__ static void dspb_seg_chain_ind(const dspb_seg_args &G) {
     const dspb_render_args &A = G.R;
     if (blockIdx.x != 0 || !kStateWords) return;
     if (!dspb_seg_level_runs(G)) return;  // launched before each warm-up level's pass 1
-    constexpr unsigned BMAX = BB ? BB : 4096u;
+    constexpr unsigned BMAX = BB ? BB : dspb_chain_max_b;
     const unsigned B = BB ? BB : A.B;
     const Parameters prm = dspb_from_global<Parameters>(A.P);
     // (block indices fit 32 bits: the host renders no longer file this way)
@@ -994,7 +875,4 @@ __device__ static void dspb_seg_chain_ind(const dspb_seg_args &G) {
 }
 #define DSPB_CHAIN_IND_KERNEL(name, CC, BB)                                            \
     extern "C" __global__ __launch_bounds__(64) void name(dspb_seg_args G) { dspb_seg_chain_ind<CC, BB>(G); }
-DSPB_CHAIN_IND_KERNEL(dspb_seg_chain_ind_c2b512, 2, 512)
-DSPB_CHAIN_IND_KERNEL(dspb_seg_chain_ind_c2, 2, 0)
-DSPB_CHAIN_IND_KERNEL(dspb_seg_chain_ind_c1, 1, 0)
-DSPB_CHAIN_IND_KERNEL(dspb_seg_chain_ind_c4, 4, 0)
+DSPB_CHAIN_IND_KERNELS(DSPB_CHAIN_IND_KERNEL)

@@ -845,20 +845,31 @@ def test_segments_pinned_to_the_host_build(torch_cuda, oracle, name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("src", ["one_pole", "counter"])
-def test_role_split_pass_edges(torch_cuda, src):
-    """The role-split pass 1 of stereo B = 512 (dspb_seg_c2b512: wave 0 the
-    callbacks, waves 1-3 the blocks) on its edge paths: one input channel for
-    two output channels (the movers load zeros for the missing one), input
-    and output rows 4 bytes off 16-byte alignment (the movers' dword path),
-    a ragged tail -- against the serial chain bit for bit, State included,
-    over two consecutive renders."""
+# (the counter's State never forgets: past the first render it is rendered in
+# segments only where its shape has a State chain kernel -- one, two or four
+# channels -- so the generic kernel's three channels take the one-pole alone)
+@pytest.mark.parametrize("src,C,B,L", [
+    ("one_pole", 2, 512, 300_001), ("counter", 2, 512, 300_001),
+    ("one_pole", 1, 256, 20_001), ("counter", 1, 256, 20_001),
+    ("one_pole", 2, 100, 20_001), ("counter", 2, 100, 20_001),
+    ("one_pole", 4, 64, 20_001), ("counter", 4, 64, 20_001),
+    ("one_pole", 3, 64, 20_001),
+], ids=lambda v: str(v))
+def test_role_split_pass_edges(torch_cuda, src, C, B, L):
+    """Pass 1 and the reruns of every segment kernel on their edge paths: the
+    role-split pass 1 of stereo B = 512 (dspb_seg_c2b512: wave 0 the
+    callbacks, waves 1-3 the blocks), the pipelined kernels of a mono, a
+    stereo (runtime B, 4 | B) and a four-channel render, and the generic
+    kernel (three channels).  One input channel fewer than output channels
+    where C > 1 (zeros are loaded for the missing one), input and output rows
+    4 bytes off 16-byte alignment (the dword path), a ragged tail -- against
+    the serial chain bit for bit, State included, over two consecutive
+    renders.  (The smaller files are 79 blocks at least: 19 segments of 4.)"""
     torch = torch_cuda
     mod = module_of(ONE_POLE_SRC if src == "one_pole" else COUNTER_SRC, f"{src}_roles_edges")
     params = mod.default_parameters()
-    C, B, L = 2, 512, 300_001
     nb = (L + B - 1) // B
-    base = torch.from_numpy(noise(1, L + 1, 71)).cuda()
+    base = torch.from_numpy(noise(max(C - 1, 1), L + 1, 71)).cuda()
     x = base[:, 1:]  # 4 bytes past a 16-byte boundary
     assert x.data_ptr() % 16 == 4
     res = {}

@@ -325,6 +325,38 @@ def test_state_reads_block_of_stock_plugins():
         assert facts_of(sine)["state_reads_block"] is False
 
 
+# ---- the driver's kernel lists ------------------------------------------------
+def _listed_kernels(families):
+    """The kernel names of csrc/plugin_driver_abi.h's X-macro lists."""
+    import re
+    text = open(os.path.join(os.path.dirname(HERE), "dsp-bench_amd", "csrc", "plugin_driver_abi.h")).read()
+    names = []
+    for fam in families:
+        body = re.search(r"#define DSPB_%s_KERNELS\(X\)((?:.*\\\n)*.*\n)" % fam, text).group(1)
+        for m in re.finditer(r"X\((\w+), *\d+, *\d+(?:, *\w+, *(\w+))?\)", body):
+            names.append(m.group(1))
+            if m.group(2) == "pf":  # reruns in a kernel of their own
+                names.append(m.group(1) + "_rerun")
+    return names
+
+
+def test_listed_segment_kernels_are_in_the_code_object(monkeypatch):
+    """A State-writing plugin compiles with and without DSPB_SEG_TIMING, and
+    every segment, walk and chain kernel of the generated lists, and the
+    check, is a symbol of either code object."""
+    import test_gpu_state_spec as ss
+    names = _listed_kernels(["SEG", "WALK", "CHAIN", "CHAIN_IND"]) + ["dspb_seg_check"]
+    assert len(names) >= 20 and "dspb_seg_c2b512_rerun" in names and "dspb_seg_rerun" not in names, names
+    monkeypatch.delenv("DSPB_SEG_TIMING", raising=False)
+    plain = dm.compile_source(ss.ONE_POLE_SRC, "one_pole_lists.cpp")
+    monkeypatch.setenv("DSPB_SEG_TIMING", "1")
+    timed = dm.compile_source(ss.ONE_POLE_SRC, "one_pole_lists.cpp")
+    assert plain != timed  # (the timing code is in)
+    for code in (plain, timed):
+        for n in names:
+            assert n.encode() + b"\0" in code and n.encode() + b".kd\0" in code, n
+
+
 # ---- the analysis options against the shipped ones --------------------------
 # dsp_module_compile analyses the callback compiled at -O2 without
 # vectorisation or unrolling, and ships code compiled at -O3 with both.  The
