@@ -20,6 +20,7 @@
 #include <tuple>
 #include <vector>
 
+#include "host_tables.hpp"
 #include "kernels.hpp"
 #include "dspbench/wav.h"
 
@@ -68,17 +69,18 @@ static DevTable dev_table(float *p, int dev) {
     });
 }
 
-struct FirTaps {  // a FIR filter's device taps + overlap-save spectrum
-    std::vector<float> taps;
-    DevTable dev;
-    float h2048r, h2048i;
-};
 
-struct IirTab {  // a biquad cascade's coefficients + state-transition powers (biquad_tables)
-    std::vector<float> coef;
+// One entry of a keyed cache of device tables (cached_table): a FIR filter's
+// taps + overlap-save spectra, keyed by the taps, or a biquad cascade's
+// coefficients + state-transition powers (biquad_tables), keyed by the
+// coefficients
+struct CachedTable {
+    std::vector<float> key;
     DevTable dev;
-    uint32_t window;  // biquad_tables' W
+    float h2048r = 0.f, h2048i = 0.f;  // FIR: H[2048] of the 8192-point spectrum
+    uint32_t window = 0;               // BIQUAD: biquad_tables' W
 };
+typedef std::vector<CachedTable> TableCache;  // oldest first
 
 // the look-back workspace of biquad_scan_kernel, one per (device, stream):
 // calls on one stream run in order, so a launch only meets words tagged with
@@ -94,8 +96,8 @@ struct DeviceRes {
     float4 *wbase = nullptr;  // (cos, sin)(theta 2l), (cos, sin)(theta (2l+1)), theta = 2 pi / 8191
     std::map<std::tuple<int, uint32_t, uint32_t, float>, float *> windows;  // (kind, N, valid, scale)
     std::map<std::pair<void *, int>, std::pair<float *, size_t>> scratch;  // per (stream, slot)
-    std::vector<FirTaps> fir;                                  // FIR filters seen (plugin_map)
-    std::vector<IirTab> iir;                                   // biquad cascades seen (plugin_map)
+    TableCache fir;                                            // FIR filters seen (plugin_map)
+    TableCache iir;                                            // biquad cascades seen (plugin_map)
     std::map<void *, IirWork> iir_work;                        // per stream
     uint32_t *iir_fb_host = nullptr, *iir_fb_dev = nullptr;  // host-mapped counter of repaired launches
     float *delta = nullptr;  // 2048 floats: 1, 0, 0, ... (compute_IR's impulse, read-only)
@@ -155,41 +157,54 @@ static int upload_table(void *dst, const void *src, size_t bytes) {
     return DSP_OK;
 }
 
+// A constant device table made on first use, with g_mu held: `slot` if it is
+// set already; else the host values from build(), uploaded to a fresh
+// allocation.  `what` names the table in the capture refusal.
+template <class T, class Build>
+static int first_use_table(T *&slot, hipStream_t s, const char *what, Build build) {
+    if (slot) return DSP_OK;
+    if (int st = refuse_capture(s, what)) return st;
+    const std::vector<T> h = build();
+    T *d = nullptr;
+    DSPB_HIP(hipMalloc(&d, sizeof(T) * h.size()));
+    if (int st = upload_table(d, h.data(), sizeof(T) * h.size())) {
+        (void)hipFree(d);
+        return st;
+    }
+    slot = d;
+    return DSP_OK;
+}
+
+static std::vector<v2f> twiddle_table() {
+    std::vector<v2f> h(8192);
+    for (int k = 0; k < 8192; ++k) {
+        const double a = -2.0 * M_PI * (double)k / 8192.0;
+        h[k] = v2f{(float)std::cos(a), (float)std::sin(a)};
+    }
+    // exact zeros / ones at the quarter turns
+    h[0] = v2f{1.f, 0.f}; h[2048] = v2f{0.f, -1.f};
+    h[4096] = v2f{-1.f, 0.f}; h[6144] = v2f{0.f, 1.f};
+    // lane-major stage twiddles of the 64 x 64 step (stft_pk.hpp, fft_pk.hpp):
+    // [8192 + 64 (j-1) + l] = T[2 l j], [8192 + 448 + 64 (j-1) + l] = T[16 l j]
+    for (int j = 1; j < 8; ++j)
+        for (int l = 0; l < 64; ++l) h.push_back(h[(2 * l * j) & 8191]);
+    for (int j = 1; j < 8; ++j)
+        for (int l = 0; l < 64; ++l) h.push_back(h[(16 * l * j) & 8191]);
+    // stft_pk.hip pairs, one float4 per (hi, lane), hi < 4:
+    // (re T[16 l hi], re T[16 l (hi + 4)], im T[16 l hi], im T[16 l (hi + 4)])
+    for (int hi = 0; hi < 4; ++hi)
+        for (int l = 0; l < 64; ++l) {
+            const v2f a = h[(16 * l * hi) & 8191], b = h[(16 * l * (hi + 4)) & 8191];
+            h.push_back(v2f{a.x, b.x});
+            h.push_back(v2f{a.y, b.y});
+        }
+    return h;
+}
+
 static int get_tw(int dev, hipStream_t s, const v2f **out) {
     std::lock_guard<std::mutex> lk(g_mu);
     DeviceRes &r = g_res[dev];
-    if (!r.tw8192) {
-        if (int st = refuse_capture(s, "the FFT twiddle table")) return st;
-        std::vector<v2f> h(8192);
-        for (int k = 0; k < 8192; ++k) {
-            const double a = -2.0 * M_PI * (double)k / 8192.0;
-            h[k] = v2f{(float)std::cos(a), (float)std::sin(a)};
-        }
-        // exact zeros / ones at the quarter turns
-        h[0] = v2f{1.f, 0.f}; h[2048] = v2f{0.f, -1.f};
-        h[4096] = v2f{-1.f, 0.f}; h[6144] = v2f{0.f, 1.f};
-        // lane-major stage twiddles of the 64 x 64 step (stft_soa.hip):
-        // [8192 + 64 (j-1) + l] = T[2 l j], [8192 + 448 + 64 (j-1) + l] = T[16 l j]
-        for (int j = 1; j < 8; ++j)
-            for (int l = 0; l < 64; ++l) h.push_back(h[(2 * l * j) & 8191]);
-        for (int j = 1; j < 8; ++j)
-            for (int l = 0; l < 64; ++l) h.push_back(h[(16 * l * j) & 8191]);
-        // stft_pk.hip pairs, one float4 per (hi, lane), hi < 4:
-        // (re T[16 l hi], re T[16 l (hi + 4)], im T[16 l hi], im T[16 l (hi + 4)])
-        for (int hi = 0; hi < 4; ++hi)
-            for (int l = 0; l < 64; ++l) {
-                const v2f a = h[(16 * l * hi) & 8191], b = h[(16 * l * (hi + 4)) & 8191];
-                h.push_back(v2f{a.x, b.x});
-                h.push_back(v2f{a.y, b.y});
-            }
-        v2f *d = nullptr;
-        DSPB_HIP(hipMalloc(&d, sizeof(v2f) * h.size()));
-        if (int st = upload_table(d, h.data(), sizeof(v2f) * h.size())) {
-            (void)hipFree(d);
-            return st;
-        }
-        r.tw8192 = d;
-    }
+    if (int st = first_use_table(r.tw8192, s, "the FFT twiddle table", twiddle_table)) return st;
     *out = r.tw8192;
     return DSP_OK;
 }
@@ -200,20 +215,20 @@ constexpr uint32_t kDeltaLen = 2048;  // the largest ir_len (4 ir_len <= 8192)
 static int get_delta(int dev, hipStream_t s, const float **out) {
     std::lock_guard<std::mutex> lk(g_mu);
     DeviceRes &r = g_res[dev];
-    if (!r.delta) {
-        if (int st = refuse_capture(s, "the impulse buffer")) return st;
+    const int st = first_use_table(r.delta, s, "the impulse buffer", [] {
         std::vector<float> h(kDeltaLen, 0.0f);
         h[0] = 1.0f;
-        float *d = nullptr;
-        DSPB_HIP(hipMalloc(&d, sizeof(float) * kDeltaLen));
-        if (int st = upload_table(d, h.data(), sizeof(float) * kDeltaLen)) {
-            (void)hipFree(d);
-            return st;
-        }
-        r.delta = d;
-    }
+        return h;
+    });
     *out = r.delta;
-    return DSP_OK;
+    return st;
+}
+
+// the cosine windows w[n] = a - b cos(2 pi n / (valid - 1))
+static void window_coefficients(int kind, double *a, double *b) {
+    *a = 0.54, *b = 0.46;
+    if (kind == DSP_WIN_HANN) *a = 0.5, *b = 0.5;
+    else if (kind == DSP_WIN_RECT) *a = 1.0, *b = 0.0;
 }
 
 // Window of length `valid` (symmetric, ref ippsWinHamming_32f convention)
@@ -221,59 +236,45 @@ static int get_delta(int dev, hipStream_t s, const float **out) {
 static int get_window(int dev, hipStream_t s, int kind, uint32_t N, uint32_t valid, const float **out,
                       double scale = 1.0) {
     std::lock_guard<std::mutex> lk(g_mu);
-    DeviceRes &r = g_res[dev];
-    auto key = std::make_tuple(kind, N, valid, (float)scale);
-    auto it = r.windows.find(key);
-    if (it != r.windows.end()) { *out = it->second; return DSP_OK; }
-    if (int st = refuse_capture(s, "a window table")) return st;
-    double a = 0.54, b = 0.46;
-    if (kind == DSP_WIN_HANN) { a = 0.5; b = 0.5; }
-    else if (kind == DSP_WIN_RECT) { a = 1.0; b = 0.0; }
-    std::vector<float> h(N, 0.f);
-    for (uint32_t n = 0; n < valid; ++n)
-        h[n] = valid == 1 ? (float)scale
-                          : (float)(scale * (a - b * std::cos(2.0 * M_PI * (double)n / (double)(valid - 1))));
-    float *d = nullptr;
-    DSPB_HIP(hipMalloc(&d, sizeof(float) * N));
-    if (int st = upload_table(d, h.data(), sizeof(float) * N)) {
-        (void)hipFree(d);
-        return st;
-    }
-    r.windows[key] = d;
-    *out = d;
-    return DSP_OK;
+    float *&slot = g_res[dev].windows[std::make_tuple(kind, N, valid, (float)scale)];
+    const int st = first_use_table(slot, s, "a window table", [&] {
+        double a, b;
+        window_coefficients(kind, &a, &b);
+        std::vector<float> h(N, 0.f);
+        for (uint32_t n = 0; n < valid; ++n)
+            h[n] = valid == 1 ? (float)scale
+                              : (float)(scale * (a - b * std::cos(2.0 * M_PI * (double)n / (double)(valid - 1))));
+        return h;
+    });
+    *out = slot;
+    return st;
 }
 
 // stft8192_pk_kernel folds DIV_BY_SQRTN and the 1/2 of the real split into
 // the window: 0.5 / sqrt(N)
 static float window_prescale(uint32_t N) { return (float)(0.5 / std::sqrt((double)N)); }
+// DIV_BY_SQRTN (dsp.cpp:74-132): every transform scales by 1 / sqrt(n)
+static float fft_scale(uint32_t n) { return (float)(1.0 / std::sqrt((double)n)); }
 
-// Inputs of the computed-window kernels (stft_soa.hip kOptWinComp): per-lane
+// Inputs of the computed-window kernels (stft_pk.hpp kOptWinComp): per-lane
 // base angles and the (pre-scaled) cosine-window coefficients.
 static int set_wincomp(int dev, hipStream_t s, int kind, Stft8kArgs *A) {
     {
         std::lock_guard<std::mutex> lk(g_mu);
         DeviceRes &r = g_res[dev];
-        if (!r.wbase) {
-            if (int st = refuse_capture(s, "the window base angles")) return st;
+        const int st = first_use_table(r.wbase, s, "the window base angles", [] {
             std::vector<float4> h(64);
             const double th = 2.0 * M_PI / 8191.0;
             for (int l = 0; l < 64; ++l)
                 h[l] = float4{(float)std::cos(th * 2 * l), (float)std::sin(th * 2 * l),
                               (float)std::cos(th * (2 * l + 1)), (float)std::sin(th * (2 * l + 1))};
-            float4 *d = nullptr;
-            DSPB_HIP(hipMalloc(&d, sizeof(float4) * 64));
-            if (int st = upload_table(d, h.data(), sizeof(float4) * 64)) {
-                (void)hipFree(d);
-                return st;
-            }
-            r.wbase = d;
-        }
+            return h;
+        });
+        if (st) return st;
         A->wbase = r.wbase;
     }
-    double a = 0.54, b = 0.46;
-    if (kind == DSP_WIN_HANN) { a = 0.5; b = 0.5; }
-    else if (kind == DSP_WIN_RECT) { a = 1.0; b = 0.0; }
+    double a, b;
+    window_coefficients(kind, &a, &b);
     const double sc = window_prescale(8192);
     A->wa = (float)(a * sc);
     A->wb = (float)(b * sc);
@@ -385,178 +386,6 @@ static bool aligned(const void *p, size_t a) { return ((uintptr_t)p % a) == 0; }
 // ---------------------------------------------------------------------------
 // plugin -> sample map
 // ---------------------------------------------------------------------------
-// FFT(taps zero-padded to 8192) / 16384 in double, laid out for
-// fir_fft.hip: for ka < 16 and lane l, 8 floats
-//   (Re H[k1], Re H[k2], Im H[k1], Im H[k2], Re H[M-k1], Re H[M-k2], Im H[M-k1], Im H[M-k2])
-// with k1 = l + 64 ka, k2 = k1 + 1024, M = 4096; then H[2048] (re, im).
-// FFT_n(taps zero-padded) in float64 (iterative radix-2, forward e^-i)
-static void taps_spectrum(const float *taps, uint32_t T, int n, std::vector<double> &re, std::vector<double> &im) {
-    re.assign(n, 0.0);
-    im.assign(n, 0.0);
-    for (uint32_t i = 0; i < T; ++i) re[i] = taps[i];
-    for (int i = 1, j = 0; i < n; ++i) {  // iterative radix-2, forward (e^-i)
-        int bit = n >> 1;
-        for (; j & bit; bit >>= 1) j ^= bit;
-        j ^= bit;
-        if (i < j) { std::swap(re[i], re[j]); std::swap(im[i], im[j]); }
-    }
-    for (int len = 2; len <= n; len <<= 1) {
-        const int hlen = len >> 1;
-        for (int k = 0; k < hlen; ++k) {
-            const double a = -2.0 * M_PI * k / len, wr = std::cos(a), wi = std::sin(a);
-            for (int s0 = 0; s0 < n; s0 += len) {
-                const double xr = re[s0 + k + hlen] * wr - im[s0 + k + hlen] * wi;
-                const double xi = re[s0 + k + hlen] * wi + im[s0 + k + hlen] * wr;
-                re[s0 + k + hlen] = re[s0 + k] - xr;
-                im[s0 + k + hlen] = im[s0 + k] - xi;
-                re[s0 + k] += xr;
-                im[s0 + k] += xi;
-            }
-        }
-    }
-}
-
-// the 8192-point table of fir_fft_kernel (kOlsHop 7168, one channel per frame)
-static void ols_table(const float *taps, uint32_t T, float *out) {
-    std::vector<double> re, im;
-    taps_spectrum(taps, T, 8192, re, im);
-    const double sc = 1.0 / 16384.0;
-    for (int ka = 0; ka < 16; ++ka)
-        for (int l = 0; l < 64; ++l) {
-            const int k1 = l + 64 * ka, k2 = k1 + 1024, m1 = 4096 - k1, m2 = 4096 - k2;
-            float *o = out + 8 * (64 * ka + l);
-            o[0] = (float)(re[k1] * sc); o[1] = (float)(re[k2] * sc);
-            o[2] = (float)(im[k1] * sc); o[3] = (float)(im[k2] * sc);
-            o[4] = (float)(re[m1] * sc); o[5] = (float)(re[m2] * sc);
-            o[6] = (float)(im[m1] * sc); o[7] = (float)(im[m2] * sc);
-        }
-    out[8192] = (float)(re[2048] * sc);
-    out[8193] = (float)(im[2048] * sc);
-}
-
-// the 4096-point table of fir_pair_kernel (two channels as one complex
-// signal): H = FFT_4096(taps) / 4096 (the inverse's scale), as float4
-// [q][lane] = (Re H[l + 64 q], Re H[l + 64 (q + 32)], Im .., Im ..), the
-// pairing of the transform's packed last combine
-static void pair_table(const float *taps, uint32_t T, float *out) {
-    std::vector<double> re, im;
-    taps_spectrum(taps, T, 4096, re, im);
-    const double sc = 1.0 / 4096.0;
-    for (int q = 0; q < 32; ++q)
-        for (int l = 0; l < 64; ++l) {
-            const int k0 = l + 64 * q, k1 = k0 + 2048;
-            float *o = out + 4 * (64 * q + l);
-            o[0] = (float)(re[k0] * sc); o[1] = (float)(re[k1] * sc);
-            o[2] = (float)(im[k0] * sc); o[3] = (float)(im[k1] * sc);
-        }
-}
-
-// IR_test (build/IR_test.cpp:47-58) runs `gain -= step` in double from the
-// float parameters.  The sequence is often exact -- every partial result a
-// double -- and then table[i] = (float)(gain - i step) is one f64 FMA, with
-// no sequential kernel.  This checks that bit for bit against the recurrence
-// itself (B host f64 subtractions, cached per parameter set).
-static bool ramp_closed_form(float gain, float step, uint32_t B) {
-    if (B > (1u << 16)) return false;
-    static std::mutex mu;
-    static struct { uint32_t g, s, B; bool ok; } last = {0, 0, 0, false};
-    uint32_t gb, sb;
-    std::memcpy(&gb, &gain, 4);
-    std::memcpy(&sb, &step, 4);
-    std::lock_guard<std::mutex> lk(mu);
-    if (last.B == B && last.g == gb && last.s == sb) return last.ok;
-    double g = gain;
-    const double s = step;
-    bool ok = true;
-    for (uint32_t i = 0; i < B && ok; ++i) {
-        const double c = std::fma(-(double)i, s, (double)gain);
-        ok = std::memcmp(&c, &g, sizeof(double)) == 0;
-        g -= s;
-    }
-    last = {gb, sb, B, ok};
-    return ok;
-}
-
-constexpr uint32_t kIirPairSections = 2;  // cascades of >= this many sections: channel pairs per wave
-
-// DSP_PLUGIN_BIQUAD (iir.hip): the cascade's zero-input state transition over
-// T = biquad_lane_samples() samples, M (D x D, D = 2 S, state = (y1, y2) per
-// section; section k's x history is section k-1's y history), simulated in
-// float64 from each unit state, then its powers:
-//   [5 S coefficients, padded to 20][M^l, l = 0..64][M^(64 k), k = 0..256]
-// Returns W, the number of preceding tiles (of 64 T samples) whose aggregate
-// reaches a tile's entering state with a weight ||M^(64 k)||_inf above 2^-48
-// (every later power below it too): 1..256, or 0 when the transition does not
-// decay that fast (then the kernel's inclusive look-back).
-static uint32_t biquad_tables(const float *cf, uint32_t S, std::vector<float> &h) {
-    const int D = 2 * (int)S, T = (int)biquad_lane_samples();
-    std::vector<double> M((size_t)D * D);
-    for (int j = 0; j < D; ++j) {
-        double Y1[4], Y2[4], X1[4], X2[4];
-        for (int k = 0; k < (int)S; ++k) {
-            Y1[k] = (2 * k == j) ? 1.0 : 0.0;
-            Y2[k] = (2 * k + 1 == j) ? 1.0 : 0.0;
-        }
-        for (int k = 0; k < (int)S; ++k) {
-            X1[k] = k ? Y1[k - 1] : 0.0;
-            X2[k] = k ? Y2[k - 1] : 0.0;
-        }
-        for (int n = 0; n < T; ++n) {
-            double v = 0.0;
-            for (int k = 0; k < (int)S; ++k) {
-                const float *c = cf + 5 * k;
-                const double y = (double)c[0] * v + (double)c[1] * X1[k] + (double)c[2] * X2[k] -
-                                 (double)c[3] * Y1[k] - (double)c[4] * Y2[k];
-                X2[k] = X1[k];
-                X1[k] = v;
-                Y2[k] = Y1[k];
-                Y1[k] = y;
-                v = y;
-            }
-        }
-        for (int k = 0; k < (int)S; ++k) {
-            M[(size_t)(2 * k) * D + j] = Y1[k];
-            M[(size_t)(2 * k + 1) * D + j] = Y2[k];
-        }
-    }
-    auto mul = [D](const std::vector<double> &a, const std::vector<double> &b) {
-        std::vector<double> r((size_t)D * D, 0.0);
-        for (int i = 0; i < D; ++i)
-            for (int k = 0; k < D; ++k)
-                for (int j = 0; j < D; ++j) r[(size_t)i * D + j] += a[(size_t)i * D + k] * b[(size_t)k * D + j];
-        return r;
-    };
-    std::vector<double> I((size_t)D * D, 0.0);
-    for (int i = 0; i < D; ++i) I[(size_t)i * D + i] = 1.0;
-    h.assign(20 + (65 + 257) * (size_t)D * D, 0.f);
-    for (uint32_t q = 0; q < 5 * S; ++q) h[q] = cf[q];
-    std::vector<double> Q = I;
-    float *o = h.data() + 20;
-    for (int l = 0; l <= 64; ++l) {
-        for (int q = 0; q < D * D; ++q) o[(size_t)l * D * D + q] = (float)Q[q];
-        Q = mul(M, Q);
-    }
-    std::vector<double> Pm = I, step = I;
-    for (int l = 0; l < 64; ++l) step = mul(M, step);  // M^64 in float64
-    o += (size_t)65 * D * D;
-    uint32_t W = 0;  // the last k <= 256 whose weight is above the cut, + 1
-    bool finite = true;
-    for (int k = 0; k <= 256; ++k) {
-        double nrm = 0.0;
-        for (int i = 0; i < D; ++i) {
-            double row = 0.0;
-            for (int j = 0; j < D; ++j) row += std::fabs(Pm[(size_t)i * D + j]);
-            nrm = std::max(nrm, row);
-        }
-        finite = finite && std::isfinite(nrm);
-        if (nrm > std::ldexp(1.0, -48)) W = (uint32_t)k + 1;
-        for (int q = 0; q < D * D; ++q) o[(size_t)k * D * D + q] = (float)Pm[q];
-        Pm = mul(step, Pm);
-    }
-    // decayed within the table: the weights of the last 64 powers are all below the cut
-    return (finite && W <= 192) ? std::max<uint32_t>(W, 1) : 0u;
-}
-
 // sleeps a BIQUAD look-back waits for a predecessor's words before it gives
 // up (a legitimate wait is a few rounds: a tile waits only for waves
 // dispatched before it); the launch is then rendered again serially
@@ -612,6 +441,34 @@ static int iir_launch(int dev, hipStream_t s, BiquadArgs *A, uint32_t sections, 
     w.epoch = w.epoch % 0xffffffffull + 1;
     A->epoch = w.epoch;
     if (int st = launch_biquad(*A, sections, nch, s)) return st;
+    return DSP_OK;
+}
+
+// The entry of `key` in a cache of at most 8 device tables, with g_mu held.
+// On a miss build(h, entry) fills the host table and the entry's payload; the
+// table is uploaded once per key, not once per render.  The caller copies
+// what it needs out of *out (the DevTable as its hold) before it unlocks.
+template <class Build>
+static int cached_table(TableCache &cache, const std::vector<float> &key, int dev, hipStream_t s, const char *what,
+                        Build build, const CachedTable **out) {
+    for (auto &e : cache)
+        if (e.key == key) { *out = &e; return DSP_OK; }
+    CachedTable e;
+    e.key = key;
+    float *d = nullptr;
+    const int st = first_use_table(d, s, what, [&] {
+        std::vector<float> h;
+        build(h, e);
+        return h;
+    });
+    if (st) return st;
+    e.dev = dev_table(d, dev);
+    // the one eviction: the oldest entry leaves, and its table is freed here
+    // unless a call still holds it -- dev_table's deleter waits for the device
+    // with g_mu held (ADVICE.md's open finding)
+    if (cache.size() >= 8) cache.erase(cache.begin());
+    cache.push_back(std::move(e));
+    *out = &cache.back();
     return DSP_OK;
 }
 
@@ -682,29 +539,20 @@ static int plugin_map(const dsp_plugin *p, uint32_t B, int dev, hipStream_t s, S
         float h2048[2] = {0.f, 0.f};
         {
             std::lock_guard<std::mutex> lk(g_mu);
-            DeviceRes &r = g_res[dev];
-            const FirTaps *ft = nullptr;
-            for (auto &e : r.fir)
-                if (e.taps == key) { ft = &e; break; }
-            if (!ft) {
-                if (int st = refuse_capture(s, "a FIR filter's device taps")) return st;
+            const CachedTable *ft = nullptr;
+            const int st = cached_table(g_res[dev].fir, key, dev, s, "a FIR filter's device taps",
+                                        [&](std::vector<float> &h, CachedTable &e) {
                 // [taps, T8][8192-point table, 8194 (+ 2 pad)][4096-point pair table, 8192]
-                std::vector<float> h(T8 + 8196 + 8192, 0.f);
+                h.assign(T8 + 8196 + 8192, 0.f);
                 std::memcpy(h.data(), key.data(), 4 * (size_t)T);
                 if (T <= 1025) {
                     ols_table(h.data(), T, h.data() + T8);
                     pair_table(h.data(), T, h.data() + T8 + 8196);
                 }
-                float *d = nullptr;
-                DSPB_HIP(hipMalloc(&d, sizeof(float) * h.size()));
-                if (int st = upload_table(d, h.data(), sizeof(float) * h.size())) {
-                    (void)hipFree(d);
-                    return st;
-                }
-                if (r.fir.size() >= 8) r.fir.erase(r.fir.begin());  // small LRU-ish cap (freed once unheld)
-                r.fir.push_back(FirTaps{key, dev_table(d, dev), h[T8 + 8192], h[T8 + 8193]});
-                ft = &r.fir.back();
-            }
+                e.h2048r = h[T8 + 8192];
+                e.h2048i = h[T8 + 8193];
+            }, &ft);
+            if (st) return st;
             *table = ft->dev;  // held by the call (copied under the lock)
             h2048[0] = ft->h2048r;
             h2048[1] = ft->h2048i;
@@ -730,24 +578,12 @@ static int plugin_map(const dsp_plugin *p, uint32_t B, int dev, hipStream_t s, S
         uint32_t window = 0;
         {
             std::lock_guard<std::mutex> lk(g_mu);
-            DeviceRes &r = g_res[dev];
-            const IirTab *it = nullptr;
-            for (auto &e : r.iir)
-                if (e.coef == key) { it = &e; break; }
-            if (!it) {
-                if (int st = refuse_capture(s, "a BIQUAD cascade's state-transition tables")) return st;
-                std::vector<float> h;
-                const uint32_t W = biquad_tables(key.data(), S, h);
-                float *d = nullptr;
-                DSPB_HIP(hipMalloc(&d, sizeof(float) * h.size()));
-                if (int st = upload_table(d, h.data(), sizeof(float) * h.size())) {
-                    (void)hipFree(d);
-                    return st;
-                }
-                if (r.iir.size() >= 8) r.iir.erase(r.iir.begin());  // as the FIR cache (freed once unheld)
-                r.iir.push_back(IirTab{key, dev_table(d, dev), W});
-                it = &r.iir.back();
-            }
+            const CachedTable *it = nullptr;
+            const int st = cached_table(g_res[dev].iir, key, dev, s, "a BIQUAD cascade's state-transition tables",
+                                        [&](std::vector<float> &h, CachedTable &e) {
+                e.window = biquad_tables(key.data(), S, biquad_lane_samples(), h);
+            }, &it);
+            if (st) return st;
             *table = it->dev;  // held by the call (copied under the lock)
             window = it->window;
         }
@@ -893,28 +729,156 @@ static void or_result(const dsp_exec *ex, uint32_t bits) {
     if (ex && ex->result) *ex->result |= bits;
 }
 
+static hipStream_t stream_of(const dsp_exec *ex) { return ex ? (hipStream_t)ex->stream : nullptr; }
+static bool host_mode(const dsp_exec *ex) { return ex && (ex->flags & DSP_EXEC_HOST_BUFFERS); }
+static uint64_t goff_of(const dsp_exec *ex) { return ex ? ex->sample_offset : 0; }
+
+// a GENERIC plugin rendered by its block class (specialize_generic) rather than its callback
+static bool by_class(MapKind plugin, MapKind rendered) {
+    return plugin == MapKind::Generic && rendered != MapKind::Generic;
+}
+
+// DSP_EXEC_VERIFY_CLASS after a render by block class: the check, and the
+// VERIFIED / RERENDERED bit.  *rerender: the caller renders again with `orig`.
+static int verify_class_result(const dsp_exec *ex, const SampleMap &orig, const SampleMap &map,
+                               const float *const *in, uint32_t in_ch, uint64_t L, float *const *out, uint32_t C,
+                               uint32_t B, hipStream_t s, bool *rerender) {
+    *rerender = false;
+    if (!by_class(orig.kind, map.kind) || !(ex && (ex->flags & DSP_EXEC_VERIFY_CLASS))) return DSP_OK;
+    bool ok = true;
+    if (int st = verify_class(orig, in, in_ch, L, out, C, B, goff_of(ex), s, &ok)) return st;
+    set_result(ex, DSP_RESULT_CLASS | (ok ? DSP_RESULT_VERIFIED : DSP_RESULT_RERENDERED));
+    *rerender = !ok;
+    return DSP_OK;
+}
+
 // ---------------------------------------------------------------------------
-// host-buffer staging (DSP_EXEC_HOST_BUFFERS)
+// argument checks (before DeviceGuard: they need no device)
 // ---------------------------------------------------------------------------
-struct Staged {
-    std::vector<float *> dev;
-    ~Staged() {
-        for (float *p : dev)
-            if (p) (void)hipFree(p);
+static int check_rows(const char *name, const float *const *rows, uint32_t n) {
+    if (n && !rows) return invalid("%s is NULL", name);
+    for (uint32_t c = 0; c < n; ++c)
+        if (!rows[c]) return invalid("%s[%u] is NULL", name, c);
+    return DSP_OK;
+}
+
+static int check_offset(const dsp_exec *ex, uint32_t B) {
+    if (ex && ex->sample_offset % B) return invalid("sample_offset must be a multiple of B");
+    return DSP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// host-buffer staging (DSP_EXEC_HOST_BUFFERS), one Stage per call.  Device
+// mode: in() / out() hand the caller's pointer back.  Host mode: a device
+// buffer each (freed when the call returns), the input copied on the call's
+// stream, the outputs copied back by copy_back(); finish() then synchronises.
+// The first failure sticks in `status` (checked once after the call's in() /
+// out()s); zero-length buffers are one float and are not copied.
+// ---------------------------------------------------------------------------
+struct Stage {
+    const bool host;
+    const hipStream_t s;
+    int status = DSP_OK;
+    struct Back { void *host; const void *dev; size_t bytes; };
+    std::vector<void *> bufs;
+    std::vector<Back> back;
+
+    explicit Stage(const dsp_exec *ex) : host(host_mode(ex)), s(stream_of(ex)) {}
+    ~Stage() {
+        for (void *p : bufs) (void)hipFree(p);
     }
-    int alloc(size_t n_floats, float **out) {
-        float *p = nullptr;
-        if (n_floats == 0) n_floats = 1;
-        DSPB_HIP(hipMalloc(&p, n_floats * sizeof(float)));
-        dev.push_back(p);
-        *out = p;
+    int alloc(size_t bytes, void **p) {  // whole floats
+        *p = nullptr;
+        if (status) return status;
+        DSPB_HIP(hipMalloc(p, std::max<size_t>((bytes + 3) & ~(size_t)3, sizeof(float))));
+        bufs.push_back(*p);
+        return DSP_OK;
+    }
+    int copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+        if (bytes) DSPB_HIP(hipMemcpyAsync(dst, src, bytes, kind, s));
+        return DSP_OK;
+    }
+    const void *in_bytes(const void *p, size_t bytes) {
+        if (!host) return p;
+        void *d;
+        if ((status = alloc(bytes, &d)) == DSP_OK) status = copy(d, p, bytes, hipMemcpyHostToDevice);
+        return d;
+    }
+    void *out_bytes(void *p, size_t bytes) {
+        if (!host) return p;
+        void *d;
+        if ((status = alloc(bytes, &d)) == DSP_OK) back.push_back(Back{p, d, bytes});
+        return d;
+    }
+    const float *in(const float *p, uint64_t n) { return (const float *)in_bytes(p, n * sizeof(float)); }
+    float *out(float *p, uint64_t n) { return (float *)out_bytes(p, n * sizeof(float)); }
+    std::vector<const float *> in_rows(const float *const *rows, uint32_t C, uint64_t n) {
+        std::vector<const float *> d(C);
+        for (uint32_t c = 0; c < C; ++c) d[c] = in(rows[c], n);
+        return d;
+    }
+    std::vector<float *> out_rows(float *const *rows, uint32_t C, uint64_t n) {
+        std::vector<float *> d(C);
+        for (uint32_t c = 0; c < C; ++c) d[c] = out(rows[c], n);
+        return d;
+    }
+    int copy_back() {  // in the order of the out()s
+        for (const Back &b : back)
+            if (int st = copy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost)) return st;
         return DSP_OK;
     }
 };
 
-static hipStream_t stream_of(const dsp_exec *ex) { return ex ? (hipStream_t)ex->stream : nullptr; }
-static bool host_mode(const dsp_exec *ex) { return ex && (ex->flags & DSP_EXEC_HOST_BUFFERS); }
-static uint64_t goff_of(const dsp_exec *ex) { return ex ? ex->sample_offset : 0; }
+// ---------------------------------------------------------------------------
+// channel groups: a kernel takes at most kMaxChannels row pointers
+// ---------------------------------------------------------------------------
+// f(c0, cn) for rows [c0, c0 + cn) of C, group after group; the first error ends the walk
+template <class F>
+static int for_groups(uint32_t C, F f) {
+    for (uint32_t c0 = 0; c0 < C; c0 += kMaxChannels) {
+        if (int st = f(c0, std::min<uint32_t>(C - c0, kMaxChannels))) return st;
+    }
+    return DSP_OK;
+}
+
+// A group's rows split for the kernels that run two channels per wavefront:
+// f(first, count, 2) for its even run of pairs (when `pairs`), then
+// f(first, count, 1) for what is left -- the odd last channel, or every row
+template <class F>
+static int for_pairs_then_rest(uint32_t cn, bool pairs, F f) {
+    const uint32_t np = pairs ? cn & ~1u : 0;  // (kMaxChannels is even)
+    if (np)
+        if (int st = f(0u, np, 2u)) return st;
+    return cn > np ? f(np, cn - np, 1u) : DSP_OK;
+}
+
+// Rows [c0, c0 + cn) of a call as a launch's pointer tables: every output
+// row, and the input rows the file has (*in_ch: one past the last of them).
+// Returns which of the pointers it touched are all `align`-byte aligned.
+enum : uint32_t { kOutAligned = 1, kInAligned = 2, kAllAligned = 3 };
+static uint32_t fill_rows(const float *const *in, uint32_t in_channels, float *const *out, uint32_t c0, uint32_t cn,
+                          ChanIn *src, uint32_t *in_ch, ChanOut *dst, size_t align = 4) {
+    uint32_t al = kAllAligned;
+    *in_ch = 0;
+    for (uint32_t j = 0; j < cn; ++j) {
+        dst->p[j] = out[c0 + j];
+        if (!aligned(out[c0 + j], align)) al &= ~kOutAligned;
+        if (c0 + j < in_channels) {
+            src->p[j] = in[c0 + j];
+            *in_ch = j + 1;
+            if (!aligned(in[c0 + j], align)) al &= ~kInAligned;
+        }
+    }
+    return al;
+}
+
+// a group's view of the call's map: a GainTable's rows start at the group's
+// first channel (module_specialize refuses C > kMaxChannels, so c0 is 0 today)
+static SampleMap group_map(const SampleMap &m, uint32_t c0) {
+    SampleMap g = m;
+    if (m.kind == MapKind::GainTable) g.table += (uint64_t)c0 * m.B;
+    return g;
+}
 
 static int finish(const dsp_exec *ex) {
     if (ex && (ex->flags & (DSP_EXEC_SYNC | DSP_EXEC_HOST_BUFFERS)))
@@ -943,24 +907,12 @@ static int render_device(const float *const *in, uint32_t in_ch, uint64_t L, flo
         // channel pairs in one wavefront (packed math) from kIirPairSections
         // sections on; an odd last channel on its own
         const bool pairs = S >= kIirPairSections;
-        for (uint32_t c0 = 0; c0 < C; c0 += kMaxChannels) {
-            const uint32_t cn = (C - c0) < (uint32_t)kMaxChannels ? (C - c0) : kMaxChannels;
-            const uint32_t np = pairs ? cn & ~1u : 0;
-            for (int part = 0; part < 2; ++part) {
-                const uint32_t first = part ? np : 0, count = part ? cn - np : np, nch = part ? 1 : 2;
-                if (!count) continue;
+        return for_groups(C, [&](uint32_t c0, uint32_t cn) {
+            return for_pairs_then_rest(cn, pairs, [&](uint32_t first, uint32_t count, uint32_t nch) {
                 BiquadArgs A{};
-                A.in_aligned16 = A.out_aligned16 = 1;
-                for (uint32_t j = 0; j < count; ++j) {
-                    const uint32_t c = c0 + first + j;
-                    A.out.p[j] = out[c];
-                    A.out_aligned16 &= aligned(out[c], 16) ? 1u : 0u;
-                    if (c < in_ch) {
-                        A.in.p[j] = in[c];
-                        A.in_ch = j + 1;
-                        A.in_aligned16 &= aligned(in[c], 16) ? 1u : 0u;
-                    }
-                }
+                const uint32_t al = fill_rows(in, in_ch, out, c0 + first, count, &A.in, &A.in_ch, &A.out, 16);
+                A.in_aligned16 = (al & kInAligned) ? 1u : 0u;
+                A.out_aligned16 = (al & kOutAligned) ? 1u : 0u;
                 A.L = L;
                 A.Ly = end;
                 A.C = count;
@@ -969,10 +921,9 @@ static int render_device(const float *const *in, uint32_t in_ch, uint64_t L, flo
                 A.Q = map.iir_tab + 20;
                 A.P = A.Q + (size_t)65 * D * D;
                 A.window = map.iir_window;
-                if (int st = iir_launch(dev, s, &A, S, nch)) return st;
-            }
-        }
-        return DSP_OK;
+                return iir_launch(dev, s, &A, S, nch);
+            });
+        });
     }
     if (map.kind == MapKind::Fir) {  // convolution from the start of the file
         if (start != 0 || goff != 0) return invalid("FIR render: whole files only (sample_offset 0)");
@@ -985,43 +936,24 @@ static int render_device(const float *const *in, uint32_t in_ch, uint64_t L, flo
             DSPB_HIP(hipGetDevice(&dev));
             int st = get_tw(dev, s, &tw);
             if (st) return st;
-            for (uint32_t c0 = 0; c0 < C; c0 += kMaxChannels) {
-                const uint32_t cn = (C - c0) < (uint32_t)kMaxChannels ? (C - c0) : kMaxChannels;
-                const uint32_t np = cn & ~1u;  // (kMaxChannels is even)
-                if (np) {
+            return for_groups(C, [&](uint32_t c0, uint32_t cn) {
+                return for_pairs_then_rest(cn, true, [&](uint32_t first, uint32_t count, uint32_t nch) {
                     FirFftArgs A{};
-                    for (uint32_t j = 0; j < np; ++j) {
-                        A.out.p[j] = out[c0 + j];
-                        if (c0 + j < in_ch) {
-                            A.in.p[j] = in[c0 + j];
-                            A.in_ch = j + 1;
-                        }
-                    }
+                    fill_rows(in, in_ch, out, c0 + first, count, &A.in, &A.in_ch, &A.out);
                     A.L = L;
                     A.Ly = end;
                     A.tw = tw;
-                    A.F = (end + kPairHop - 1) / kPairHop;
-                    A.H = map.pairH;
-                    if ((st = launch_fir_pair(A, np, s))) return st;
-                }
-                if (cn & 1) {
-                    const uint32_t c = c0 + cn - 1;
-                    FirFftArgs A{};
-                    A.out.p[0] = out[c];
-                    if (c < in_ch) {
-                        A.in.p[0] = in[c];
-                        A.in_ch = 1;
+                    if (nch == 2) {
+                        A.F = (end + kPairHop - 1) / kPairHop;
+                        A.H = map.pairH;
+                        return launch_fir_pair(A, count, s);
                     }
-                    A.L = L;
-                    A.Ly = end;
                     A.F = (end + 7167) / 7168;
                     A.H = map.olsH;
                     A.h2048 = v2f{map.olsH2048[0], map.olsH2048[1]};
-                    A.tw = tw;
-                    if ((st = launch_fir_fft(A, 1, s))) return st;
-                }
-            }
-            return DSP_OK;
+                    return launch_fir_fft(A, 1, s);
+                });
+            });
         }
         for (uint32_t c = 0; c < C; ++c) {
             int st = launch_fir(c < in_ch ? in[c] : nullptr, L, out[c], end, map.taps, map.ntaps8,
@@ -1030,30 +962,17 @@ static int render_device(const float *const *in, uint32_t in_ch, uint64_t L, flo
         }
         return DSP_OK;
     }
-    for (uint32_t c0 = 0; c0 < C; c0 += kMaxChannels) {
-        const uint32_t cn = (C - c0) < (uint32_t)kMaxChannels ? (C - c0) : kMaxChannels;
+    return for_groups(C, [&](uint32_t c0, uint32_t cn) {
         RenderArgs A{};
-        bool vec = (start % 4) == 0;
-        A.in_ch = 0;
-        for (uint32_t j = 0; j < cn; ++j) {
-            A.out.p[j] = out[c0 + j];
-            vec = vec && aligned(out[c0 + j], 16);
-            if (c0 + j < in_ch) {
-                A.in.p[j] = in[c0 + j];
-                A.in_ch = j + 1;
-                vec = vec && aligned(in[c0 + j], 16);
-            }
-        }
+        const bool vec = fill_rows(in, in_ch, out, c0, cn, &A.in, &A.in_ch, &A.out, 16) == kAllAligned &&
+                         (start % 4) == 0;
         A.L = L;
         A.start = start;
         A.end = end;
-        A.map = map;
-        if (map.kind == MapKind::GainTable) A.map.table += (uint64_t)c0 * map.B;  // this group's rows
+        A.map = group_map(map, c0);
         A.goff = goff;
-        int st = launch_render(A, cn, vec, s);
-        if (st) return st;
-    }
-    return DSP_OK;
+        return launch_render(A, cn, vec, s);
+    });
 }
 
 static int check_stft_args(uint32_t N, uint32_t H, uint32_t K, uint64_t ld, int32_t window) {
@@ -1064,6 +983,46 @@ static int check_stft_args(uint32_t N, uint32_t H, uint32_t K, uint64_t ld, int3
     if (K == 0 || (K > N / 2 + 1 && K != N)) return invalid("K=%u must be <= N/2+1 or == N", K);
     if (ld < K) return invalid("ld=%llu < K=%u", (unsigned long long)ld, K);
     return DSP_OK;
+}
+
+// The memory-source part of an 8192-point STFT launch (launch_stft): tables,
+// scale and frame geometry.  wincomp: the DSP_WIN_* kind whose computed form
+// the launch may use (set_wincomp: a first-use table), or -1 for none.
+static int stft8k_args(Stft8kArgs *A, int dev, hipStream_t s, const v2f *tw, const float *win, uint64_t F,
+                       uint32_t H, uint32_t K, uint64_t ld, uint32_t valid, int wincomp) {
+    A->F = F;
+    A->H = H;
+    A->K = K;
+    A->ld = ld;
+    A->valid = valid;
+    A->win2 = reinterpret_cast<const v2f *>(win);
+    A->tw = tw;
+    A->scale = fft_scale(8192);
+    return wincomp >= 0 ? set_wincomp(dev, s, wincomp, A) : DSP_OK;
+}
+
+static GenericFftArgs fft_args(const v2f *tw, uint32_t n, int dir) {
+    GenericFftArgs A{};
+    A.n = n;
+    A.log2n = ilog2(n);
+    A.dir = dir;
+    A.tw = tw;
+    A.scale = fft_scale(n);
+    return A;
+}
+
+// frames of `valid` samples every `hop`, windowed and zero-padded to n -> K
+// magnitudes per row of ld floats; the caller sets sig and mag
+static GenericFftArgs fft_mag_args(const v2f *tw, const float *win, uint32_t n, uint32_t valid, uint64_t hop,
+                                   uint32_t K, uint64_t ld) {
+    GenericFftArgs A = fft_args(tw, n, -1);
+    A.frame_hop = hop;
+    A.valid = valid;
+    A.win = win;
+    A.K = K;
+    A.ld = ld;
+    A.mode = 2;
+    return A;
 }
 
 static int stft_device(const float *const *in, uint32_t C, uint64_t L, uint32_t N, uint32_t H,
@@ -1079,53 +1038,23 @@ static int stft_device(const float *const *in, uint32_t C, uint64_t L, uint32_t 
     for (uint32_t c = 0; c < C; ++c) fast = fast && aligned(in[c], 8);
     st = get_window(dev, s, window, N, N, &win, fast ? window_prescale(N) : 1.0);
     if (st) return st;
-    for (uint32_t c0 = 0; c0 < C; c0 += kMaxChannels) {
-        const uint32_t cn = (C - c0) < (uint32_t)kMaxChannels ? (C - c0) : kMaxChannels;
-        if (fast) {
-            Stft8kArgs A{};
-            for (uint32_t j = 0; j < cn; ++j) {
-                A.in.p[j] = in[c0 + j];
-                A.mag.p[j] = mag[c0 + j];
-            }
-            A.in_ch = cn;
-            A.L = L;
-            A.F = F;
-            A.H = H;
-            A.K = K;
-            A.ld = ld;
-            A.valid = N;
-            A.win2 = reinterpret_cast<const v2f *>(win);
-            A.tw = tw;
-            A.scale = (float)(1.0 / std::sqrt((double)N));
-            if ((st = set_wincomp(dev, s, window, &A))) return st;
-            TimedLaunch tl{};
-            if ((st = timing_begin(s, &tl))) return st;
-            st = launch_stft(A, cn, false, s);
-            if (st) return st;
-            // algorithmic bytes: frame input read once per hop + magnitudes
-            st = timing_end(s, &tl, (uint64_t)cn * F * ((uint64_t)H * 4 + (uint64_t)K * 4));
-        } else {
-            GenericFftArgs A{};
-            for (uint32_t j = 0; j < cn; ++j) {
-                A.sig.p[j] = in[c0 + j];
-                A.mag.p[j] = mag[c0 + j];
-            }
-            A.frame_hop = H;
-            A.valid = N;
-            A.win = win;
-            A.n = N;
-            A.log2n = ilog2(N);
-            A.dir = -1;
-            A.tw = tw;
-            A.scale = (float)(1.0 / std::sqrt((double)N));
-            A.K = K;
-            A.ld = ld;
-            A.mode = 2;
-            st = launch_fft_generic(A, F, cn, s);
+    return for_groups(C, [&](uint32_t c0, uint32_t cn) {
+        uint32_t in_ch;  // = cn: every row is signal
+        if (!fast) {
+            GenericFftArgs A = fft_mag_args(tw, win, N, N, H, K, ld);
+            fill_rows(in, C, mag, c0, cn, &A.sig, &in_ch, &A.mag);
+            return launch_fft_generic(A, F, cn, s);
         }
-        if (st) return st;
-    }
-    return DSP_OK;
+        Stft8kArgs A{};
+        fill_rows(in, C, mag, c0, cn, &A.in, &A.in_ch, &A.mag);
+        A.L = L;
+        if (int e = stft8k_args(&A, dev, s, tw, win, F, H, K, ld, N, window)) return e;
+        TimedLaunch tl{};
+        if (int e = timing_begin(s, &tl)) return e;
+        if (int e = launch_stft(A, cn, false, s)) return e;
+        // algorithmic bytes: frame input read once per hop + magnitudes
+        return timing_end(s, &tl, (uint64_t)cn * F * ((uint64_t)H * 4 + (uint64_t)K * 4));
+    });
 }
 
 // GENERIC render + STFT: the plugin's own callback renders the whole file
@@ -1254,7 +1183,7 @@ int dsp_biquad_plan(const float *coef, uint32_t sections, uint32_t *window) {
     for (uint32_t q = 0; q < 5 * sections; ++q)
         if (!std::isfinite(coef[q])) return invalid("BIQUAD coefficients must be finite");
     std::vector<float> h;
-    *window = biquad_tables(coef, sections, h);
+    *window = biquad_tables(coef, sections, biquad_lane_samples(), h);
     return DSP_OK;
 }
 
@@ -1269,42 +1198,22 @@ int dsp_render_offline(const float *const *in, uint32_t in_channels, uint64_t L,
     // (only a GENERIC plugin reads the sample rate)
     if (B == 0) return invalid("block size B must be > 0");
     if (C == 0) return DSP_OK;
-    if (!out) return invalid("out is NULL");
-    for (uint32_t c = 0; c < C; ++c)
-        if (!out[c]) return invalid("out[%u] is NULL", c);
-    if (in_channels && !in) return invalid("in is NULL");
-    for (uint32_t c = 0; c < in_channels; ++c)
-        if (!in[c]) return invalid("in[%u] is NULL", c);
-    if (ex && ex->sample_offset % B) return invalid("sample_offset must be a multiple of B");
+    int st;
+    if ((st = check_rows("out", out, C)) || (st = check_rows("in", in, in_channels)) || (st = check_offset(ex, B)))
+        return st;
     DeviceGuard g(ex);
     if (g.status) return g.status;
     hipStream_t s = stream_of(ex);
     const uint64_t nblocks = (L + B - 1) / B;
     const uint64_t Lr = nblocks * B;
 
-    std::vector<const float *> din(in_channels);
-    std::vector<float *> dout(C);
-    Staged stage;
-    if (host_mode(ex)) {
-        for (uint32_t c = 0; c < in_channels; ++c) {
-            float *d;
-            int st = stage.alloc(L, &d);
-            if (st) return st;
-            DSPB_HIP(hipMemcpyAsync(d, in[c], L * sizeof(float), hipMemcpyHostToDevice, s));
-            din[c] = d;
-        }
-        for (uint32_t c = 0; c < C; ++c) {
-            int st = stage.alloc(Lr, &dout[c]);
-            if (st) return st;
-        }
-    } else {
-        for (uint32_t c = 0; c < in_channels; ++c) din[c] = in[c];
-        for (uint32_t c = 0; c < C; ++c) dout[c] = out[c];
-    }
+    Stage stage(ex);
+    const std::vector<const float *> din = stage.in_rows(in, in_channels, L);
+    const std::vector<float *> dout = stage.out_rows(out, C, Lr);
+    if (stage.status) return stage.status;
     SpecHold hold;  // released after the call's launches
     SampleMap map;
-    int st = plugin_map(plugin, B, g.dev, s, &map, sr, ex ? ex->flags : 0, &hold.table);
-    if (st) return st;
+    if ((st = plugin_map(plugin, B, g.dev, s, &map, sr, ex ? ex->flags : 0, &hold.table))) return st;
     const SampleMap orig = map;
     if ((st = specialize_generic(&map, C, B, s, ex, rows_overlap(din.data(), in_channels, L, dout.data(), C, Lr), &hold)))
         return st;
@@ -1317,23 +1226,12 @@ int dsp_render_offline(const float *const *in, uint32_t in_channels, uint64_t L,
         if (map.kind != MapKind::Ramp) bytes += (uint64_t)std::min(in_channels, C) * L * 4;
         if ((st = timing_end(s, &tl, bytes))) return st;
     }
-    if (orig.kind == MapKind::Generic && map.kind != MapKind::Generic) {
-        uint32_t res = DSP_RESULT_CLASS;
-        if (ex && (ex->flags & DSP_EXEC_VERIFY_CLASS)) {
-            bool ok = true;
-            if ((st = verify_class(orig, din.data(), in_channels, L, dout.data(), C, B, goff_of(ex), s, &ok))) return st;
-            res |= ok ? DSP_RESULT_VERIFIED : DSP_RESULT_RERENDERED;
-            if (!ok && (st = render_device(din.data(), in_channels, L, dout.data(), C, B, orig, 0, goff_of(ex), s)))
-                return st;
-        }
-        set_result(ex, res);
-    } else {
-        set_result(ex, 0);
-    }
-    if (host_mode(ex))
-        for (uint32_t c = 0; c < C; ++c)
-            DSPB_HIP(hipMemcpyAsync(out[c], dout[c], Lr * sizeof(float), hipMemcpyDeviceToHost, s));
-    return finish(ex);
+    set_result(ex, by_class(orig.kind, map.kind) ? DSP_RESULT_CLASS : 0u);
+    bool rerender = false;
+    if ((st = verify_class_result(ex, orig, map, din.data(), in_channels, L, dout.data(), C, B, s, &rerender))) return st;
+    if (rerender && (st = render_device(din.data(), in_channels, L, dout.data(), C, B, orig, 0, goff_of(ex), s)))
+        return st;
+    return (st = stage.copy_back()) ? st : finish(ex);
 }
 
 int dsp_render_loop(const float *const *in, uint32_t in_channels, uint64_t L, uint64_t cursor,
@@ -1345,50 +1243,36 @@ int dsp_render_loop(const float *const *in, uint32_t in_channels, uint64_t L, ui
                                                    (unsigned long long)L);
     if (cursor_out) *cursor_out = in_channels ? (uint64_t)((cursor + (unsigned __int128)nblocks * B) % L) : cursor;
     if (C == 0 || nblocks == 0) return DSP_OK;
-    if (!out) return invalid("out is NULL");
-    for (uint32_t c = 0; c < C; ++c)
-        if (!out[c]) return invalid("out[%u] is NULL", c);
-    if (in_channels && !in) return invalid("in is NULL");
-    for (uint32_t c = 0; c < in_channels; ++c)
-        if (!in[c]) return invalid("in[%u] is NULL", c);
+    int st;
+    if ((st = check_rows("out", out, C)) || (st = check_rows("in", in, in_channels))) return st;
     if (host_mode(ex)) return invalid("dsp_render_loop: device buffers only");
-    if (ex && ex->sample_offset % B) return invalid("sample_offset must be a multiple of B");
+    if ((st = check_offset(ex, B))) return st;
     DeviceGuard g(ex);
     if (g.status) return g.status;
     hipStream_t s = stream_of(ex);
     const uint64_t Lr = nblocks * B;
     SpecHold hold;  // released after the call's launches
     SampleMap map;
-    int st = plugin_map(plugin, B, g.dev, s, &map, sr, ex ? ex->flags : 0, &hold.table);
-    if (st) return st;
+    if ((st = plugin_map(plugin, B, g.dev, s, &map, sr, ex ? ex->flags : 0, &hold.table))) return st;
     // DSP_EXEC_VERIFY_CLASS: loop mode renders with the callback on every
     // block (as an in-place call does) rather than a class it would not check
     const bool verify = ex && (ex->flags & DSP_EXEC_VERIFY_CLASS);
     const MapKind before = map.kind;
     if ((st = specialize_generic(&map, C, B, s, ex, verify, &hold))) return st;
-    set_result(ex, before == MapKind::Generic && map.kind != MapKind::Generic ? DSP_RESULT_CLASS : 0u);
+    set_result(ex, by_class(before, map.kind) ? DSP_RESULT_CLASS : 0u);
     if ((st = ensure_ramp_table(map, s))) return st;
     const uint32_t in_ch = std::min(in_channels, C);  // channels_to_write (audio.cpp:66)
     auto wrap = [&](const float *const *src, float *const *dst, uint32_t nc, const SampleMap &m) -> int {
-        for (uint32_t c0 = 0; c0 < nc; c0 += kMaxChannels) {
-            const uint32_t cn = (nc - c0) < (uint32_t)kMaxChannels ? (nc - c0) : kMaxChannels;
+        return for_groups(nc, [&](uint32_t c0, uint32_t cn) {
             RenderArgs A{};
-            for (uint32_t j = 0; j < cn; ++j) {
-                A.out.p[j] = dst[c0 + j];
-                if (c0 + j < in_ch) {
-                    A.in.p[j] = src[c0 + j];
-                    A.in_ch = j + 1;
-                }
-            }
+            fill_rows(src, in_ch, dst, c0, cn, &A.in, &A.in_ch, &A.out);
             A.L = L;
             A.start = 0;
             A.end = Lr;
-            A.map = m;
-            if (m.kind == MapKind::GainTable) A.map.table += (uint64_t)c0 * m.B;  // this group's rows
+            A.map = group_map(m, c0);
             A.goff = goff_of(ex);
-            if (int e = launch_render_wrap(A, cn, cursor, s)) return e;
-        }
-        return DSP_OK;
+            return launch_render_wrap(A, cn, cursor, s);
+        });
     };
     if (map.kind == MapKind::Noop || map.kind == MapKind::Gain || map.kind == MapKind::Ramp ||
         map.kind == MapKind::GainTable)
@@ -1425,26 +1309,12 @@ int dsp_stft_magnitude(const float *const *in, uint32_t C, uint64_t L, uint32_t 
     if (g.status) return g.status;
     hipStream_t s = stream_of(ex);
     const uint64_t F = dsp_stft_frame_count(L, N, H);
-    std::vector<const float *> din(C);
-    std::vector<float *> dmag(C);
-    Staged stage;
-    if (host_mode(ex)) {
-        for (uint32_t c = 0; c < C; ++c) {
-            float *d;
-            if ((st = stage.alloc(L, &d))) return st;
-            DSPB_HIP(hipMemcpyAsync(d, in[c], L * sizeof(float), hipMemcpyHostToDevice, s));
-            din[c] = d;
-            if ((st = stage.alloc(F * ld, &dmag[c]))) return st;
-        }
-    } else {
-        for (uint32_t c = 0; c < C; ++c) { din[c] = in[c]; dmag[c] = mag[c]; }
-    }
-    st = stft_device(din.data(), C, L, N, H, window, K, dmag.data(), ld, g.dev, s);
-    if (st) return st;
-    if (host_mode(ex) && F)
-        for (uint32_t c = 0; c < C; ++c)
-            DSPB_HIP(hipMemcpyAsync(mag[c], dmag[c], F * ld * sizeof(float), hipMemcpyDeviceToHost, s));
-    return finish(ex);
+    Stage stage(ex);
+    const std::vector<const float *> din = stage.in_rows(in, C, L);
+    const std::vector<float *> dmag = stage.out_rows(mag, C, F * ld);  // (F == 0: nothing to copy back)
+    if (stage.status) return stage.status;
+    if ((st = stft_device(din.data(), C, L, N, H, window, K, dmag.data(), ld, g.dev, s))) return st;
+    return (st = stage.copy_back()) ? st : finish(ex);
 }
 
 int dsp_render_stft(const float *const *in, uint32_t in_channels, uint64_t L,
@@ -1459,10 +1329,7 @@ int dsp_render_stft(const float *const *in, uint32_t in_channels, uint64_t L,
     if (!out || !mag) return invalid("out / mag is NULL");
     for (uint32_t c = 0; c < C; ++c)
         if (!out[c] || !mag[c]) return invalid("out[%u] / mag[%u] is NULL", c, c);
-    if (in_channels && !in) return invalid("in is NULL");
-    for (uint32_t c = 0; c < in_channels; ++c)
-        if (!in[c]) return invalid("in[%u] is NULL", c);
-    if (ex && ex->sample_offset % B) return invalid("sample_offset must be a multiple of B");
+    if ((st = check_rows("in", in, in_channels)) || (st = check_offset(ex, B))) return st;
     DeviceGuard g(ex);
     if (g.status) return g.status;
     hipStream_t s = stream_of(ex);
@@ -1470,24 +1337,11 @@ int dsp_render_stft(const float *const *in, uint32_t in_channels, uint64_t L,
     const uint64_t Lr = nblocks * B;
     const uint64_t F = dsp_stft_frame_count(Lr, N, H);
 
-    std::vector<const float *> din(in_channels);
-    std::vector<float *> dout(C), dmag(C);
-    Staged stage;
-    if (host_mode(ex)) {
-        for (uint32_t c = 0; c < in_channels; ++c) {
-            float *d;
-            if ((st = stage.alloc(L, &d))) return st;
-            DSPB_HIP(hipMemcpyAsync(d, in[c], L * sizeof(float), hipMemcpyHostToDevice, s));
-            din[c] = d;
-        }
-        for (uint32_t c = 0; c < C; ++c) {
-            if ((st = stage.alloc(Lr, &dout[c]))) return st;
-            if ((st = stage.alloc(F * ld, &dmag[c]))) return st;
-        }
-    } else {
-        for (uint32_t c = 0; c < in_channels; ++c) din[c] = in[c];
-        for (uint32_t c = 0; c < C; ++c) { dout[c] = out[c]; dmag[c] = mag[c]; }
-    }
+    Stage stage(ex);
+    const std::vector<const float *> din = stage.in_rows(in, in_channels, L);
+    const std::vector<float *> dout = stage.out_rows(out, C, Lr);
+    const std::vector<float *> dmag = stage.out_rows(mag, C, F * ld);  // (F == 0: nothing to copy back)
+    if (stage.status) return stage.status;
     SpecHold hold;  // released after the call's launches
     SampleMap map;
     if ((st = plugin_map(plugin, B, g.dev, s, &map, sr, ex ? ex->flags : 0, &hold.table))) return st;
@@ -1495,7 +1349,7 @@ int dsp_render_stft(const float *const *in, uint32_t in_channels, uint64_t L,
     if ((st = specialize_generic(&map, C, B, s, ex, rows_overlap(din.data(), in_channels, L, dout.data(), C, Lr), &hold)))
         return st;
     const uint64_t goff = goff_of(ex);
-    set_result(ex, orig.kind == MapKind::Generic && map.kind != MapKind::Generic ? DSP_RESULT_CLASS : 0u);
+    set_result(ex, by_class(orig.kind, map.kind) ? DSP_RESULT_CLASS : 0u);
 
     bool fused = (N == 8192) && (H % 128 == 0) && (H <= N) && (goff % 2 == 0) && F > 0 &&
                  map.kind != MapKind::Fir && map.kind != MapKind::Generic && map.kind != MapKind::Biquad;
@@ -1526,30 +1380,13 @@ int dsp_render_stft(const float *const *in, uint32_t in_channels, uint64_t L,
         if ((st = get_tw(g.dev, s, &tw))) return st;
         if ((st = get_window(g.dev, s, window, N, N, &win, window_prescale(N)))) return st;
         bool tail_in_kernel = false, reused = false;
-        for (uint32_t c0 = 0; c0 < C; c0 += kMaxChannels) {
-            const uint32_t cn = (C - c0) < (uint32_t)kMaxChannels ? (C - c0) : kMaxChannels;
+        st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
             Stft8kArgs A{};
-            A.in_ch = 0;
-            for (uint32_t j = 0; j < cn; ++j) {
-                A.out.p[j] = dout[c0 + j];
-                A.mag.p[j] = dmag[c0 + j];
-                if (c0 + j < in_channels) {
-                    A.in.p[j] = din[c0 + j];
-                    A.in_ch = j + 1;
-                }
-            }
+            fill_rows(din.data(), in_channels, dout.data(), c0, cn, &A.in, &A.in_ch, &A.out);
+            std::copy_n(dmag.data() + c0, cn, A.mag.p);
             A.L = L;
-            A.F = F;
-            A.H = H;
-            A.K = K;
-            A.ld = ld;
-            A.valid = N;
-            A.win2 = reinterpret_cast<const v2f *>(win);
-            A.tw = tw;
-            A.scale = (float)(1.0 / std::sqrt((double)N));
-            if ((st = set_wincomp(g.dev, s, window, &A))) return st;
-            A.map = map;
-            if (map.kind == MapKind::GainTable) A.map.table += (uint64_t)c0 * map.B;  // this group's rows
+            if (int e = stft8k_args(&A, g.dev, s, tw, win, F, H, K, ld, N, window)) return e;
+            A.map = group_map(map, c0);
             A.goff = goff;
             // the PER kernel also renders the tail no frame owns
             if (stft8192_pk_per_path(A, true)) A.tail_end = Lr, tail_in_kernel = true;
@@ -1562,16 +1399,17 @@ int dsp_render_stft(const float *const *in, uint32_t in_channels, uint64_t L,
             A.run = every_frame ? 1u : stft8192_pk_frame_run(A, true, cn, g_frame_run.load());
             if (A.run > 1) reused = true;
             TimedLaunch tl{};
-            if ((st = timing_begin(s, &tl))) return st;
-            if ((st = launch_stft(A, cn, true, s))) return st;
+            if (int e = timing_begin(s, &tl)) return e;
+            if (int e = launch_stft(A, cn, true, s)) return e;
             // algorithmic bytes: render write 4 B + magnitudes 4 K/H B
             // per hop sample, plus the file read when the map uses its input
             const uint64_t hop_samples = (uint64_t)cn * F * H;
             uint64_t bytes = hop_samples * 4 + (uint64_t)cn * F * K * 4;
             if (map.kind != MapKind::Ramp) bytes += (uint64_t)A.in_ch * F * H * 4;
             if (A.tail_end) bytes += (uint64_t)cn * (A.tail_end - F * (uint64_t)H) * 4;
-            if ((st = timing_end(s, &tl, bytes))) return st;
-        }
+            return timing_end(s, &tl, bytes);
+        });
+        if (st) return st;
         if (reused) or_result(ex, DSP_RESULT_FRAME_REUSE);
         // the render tail no frame owns: [F*H, Lr)
         if (!tail_in_kernel) {
@@ -1579,23 +1417,12 @@ int dsp_render_stft(const float *const *in, uint32_t in_channels, uint64_t L,
             if (st) return st;
         }
     }
-    if (orig.kind == MapKind::Generic && map.kind != MapKind::Generic && ex && (ex->flags & DSP_EXEC_VERIFY_CLASS)) {
-        bool ok = true;
-        if ((st = verify_class(orig, din.data(), in_channels, L, dout.data(), C, B, goff, s, &ok))) return st;
-        set_result(ex, DSP_RESULT_CLASS | (ok ? DSP_RESULT_VERIFIED : DSP_RESULT_RERENDERED));
-        if (!ok && (st = generic_render_stft(din.data(), in_channels, L, dout.data(), C, B, orig, N, H, window, K,
-                                             dmag.data(), ld, goff, g.dev, s)))
-            return st;
-    }
-    if (host_mode(ex)) {
-        for (uint32_t c = 0; c < C; ++c) {
-            DSPB_HIP(hipMemcpyAsync(out[c], dout[c], Lr * sizeof(float), hipMemcpyDeviceToHost, s));
-            if (F)
-                DSPB_HIP(hipMemcpyAsync(mag[c], dmag[c], F * ld * sizeof(float),
-                                        hipMemcpyDeviceToHost, s));
-        }
-    }
-    return finish(ex);
+    bool rerender = false;
+    if ((st = verify_class_result(ex, orig, map, din.data(), in_channels, L, dout.data(), C, B, s, &rerender))) return st;
+    if (rerender && (st = generic_render_stft(din.data(), in_channels, L, dout.data(), C, B, orig, N, H, window, K,
+                                              dmag.data(), ld, goff, g.dev, s)))
+        return st;
+    return (st = stage.copy_back()) ? st : finish(ex);
 }
 
 int dsp_ir_analysis(const dsp_plugin *plugin, uint32_t C, float sr, uint32_t ir_len,
@@ -1603,36 +1430,29 @@ int dsp_ir_analysis(const dsp_plugin *plugin, uint32_t C, float sr, uint32_t ir_
     if (C == 0 || ir_len == 0) return invalid("C and ir_len must be > 0");
     if (!is_pow2(ir_len) || 4ull * ir_len > 8192) return invalid("4*ir_len must be a power of two <= 8192");
     if (!ir_out || !mag) return invalid("ir_out / mag is NULL");
-    for (uint32_t c = 0; c < C; ++c)
-        if (!ir_out[c]) return invalid("ir_out[%u] is NULL", c);
+    int st;
+    if ((st = check_rows("ir_out", ir_out, C))) return st;
     if (plugin && plugin->kind == DSP_PLUGIN_GENERIC && C > (uint32_t)kMaxChannels)
         return invalid("GENERIC plugin: IR analysis of 1..%d channels", kMaxChannels);
     DeviceGuard g(ex);
     if (g.status) return g.status;
     hipStream_t s = stream_of(ex);
     const uint32_t n = 4 * ir_len;
-    std::vector<float *> dir(C);
-    float *dmag = mag;
-    Staged stage;
-    int st;
-    if (host_mode(ex)) {
-        for (uint32_t c = 0; c < C; ++c)
-            if ((st = stage.alloc(ir_len, &dir[c]))) return st;
-        if ((st = stage.alloc(n, &dmag))) return st;
-    } else {
-        for (uint32_t c = 0; c < C; ++c) dir[c] = ir_out[c];
-    }
+    Stage stage(ex);
+    const std::vector<float *> dir = stage.out_rows(ir_out, C, ir_len);
+    float *dmag = stage.out(mag, n);
+    if (stage.status) return stage.status;
     // compute_IR (plugin.cpp:27-34): IR[c] = delta, then one callback of ir_len
     SampleMap map;
     DevTable table;  // held until the call's launches are enqueued
     if ((st = plugin_map(plugin, ir_len, g.dev, s, &map, sr, ex ? ex->flags : 0, &table))) return st;
     if (map.kind == MapKind::Generic) {  // the impulse in place, a fresh scratch State, one callback
-        for (uint32_t c0 = 0; c0 < C; c0 += kMaxChannels) {
-            const uint32_t cn = (C - c0) < (uint32_t)kMaxChannels ? (C - c0) : kMaxChannels;
+        st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
             ChanOut imp{};
-            for (uint32_t j = 0; j < cn; ++j) imp.p[j] = dir[c0 + j];
-            if ((st = launch_impulse(imp, cn, ir_len, s))) return st;
-        }
+            std::copy_n(dir.data() + c0, cn, imp.p);
+            return launch_impulse(imp, cn, ir_len, s);
+        });
+        if (st) return st;
         if ((st = module_ir((::dsp_module *)map.module, map.gparams, map.gparams_size, dir.data(), C, ir_len, sr, s)))
             return st;
     } else {  // map plugins: render the read-only impulse into IR[c], one launch
@@ -1649,44 +1469,23 @@ int dsp_ir_analysis(const dsp_plugin *plugin, uint32_t C, float sr, uint32_t ir_
     const bool fast_ir = n == 8192 && aligned(dir[0], 8);
     if ((st = get_window(g.dev, s, DSP_WIN_HAMMING, n, ir_len, &win, fast_ir ? window_prescale(n) : 1.0)))
         return st;
+    // one frame of ir_len samples, all n bins, as the reference stores them (dsp.cpp:65)
     if (fast_ir) {
         Stft8kArgs A{};
         A.in.p[0] = dir[0];
         A.in_ch = 1;
         A.L = ir_len;
         A.mag.p[0] = dmag;
-        A.F = 1;
-        A.H = n;
-        A.K = n;  // all bins, as the reference stores them (dsp.cpp:65)
-        A.ld = n;
-        A.valid = ir_len;
-        A.win2 = reinterpret_cast<const v2f *>(win);
-        A.tw = tw;
-        A.scale = (float)(1.0 / std::sqrt((double)n));
+        // (no computed window: its base angles would be one more first-use table)
+        if ((st = stft8k_args(&A, g.dev, s, tw, win, 1, n, n, n, ir_len, -1))) return st;
         if ((st = launch_stft(A, 1, false, s))) return st;
     } else {
-        GenericFftArgs A{};
+        GenericFftArgs A = fft_mag_args(tw, win, n, ir_len, 0, n, n);
         A.sig.p[0] = dir[0];
-        A.frame_hop = 0;
-        A.valid = ir_len;
-        A.win = win;
-        A.n = n;
-        A.log2n = ilog2(n);
-        A.dir = -1;
-        A.tw = tw;
-        A.scale = (float)(1.0 / std::sqrt((double)n));
         A.mag.p[0] = dmag;
-        A.K = n;
-        A.ld = n;
-        A.mode = 2;
         if ((st = launch_fft_generic(A, 1, 1, s))) return st;
     }
-    if (host_mode(ex)) {
-        for (uint32_t c = 0; c < C; ++c)
-            DSPB_HIP(hipMemcpyAsync(ir_out[c], dir[c], ir_len * sizeof(float), hipMemcpyDeviceToHost, s));
-        DSPB_HIP(hipMemcpyAsync(mag, dmag, n * sizeof(float), hipMemcpyDeviceToHost, s));
-    }
-    return finish(ex);
+    return (st = stage.copy_back()) ? st : finish(ex);
 }
 
 static int fft_service(const float *re_in, const float *im_in, float *re_out, float *im_out,
@@ -1698,40 +1497,16 @@ static int fft_service(const float *re_in, const float *im_in, float *re_out, fl
     const v2f *tw = nullptr;
     int st = get_tw(g.dev, s, &tw);
     if (st) return st;
-    Staged stage;
-    const float *dre = re_in, *dim = im_in;
-    float *dro = re_out, *dio = im_out;
-    if (host_mode(ex)) {
-        float *a, *b;
-        if ((st = stage.alloc(n, &a))) return st;
-        DSPB_HIP(hipMemcpyAsync(a, re_in, n * sizeof(float), hipMemcpyHostToDevice, s));
-        dre = a;
-        if (im_in) {
-            if ((st = stage.alloc(n, &b))) return st;
-            DSPB_HIP(hipMemcpyAsync(b, im_in, n * sizeof(float), hipMemcpyHostToDevice, s));
-            dim = b;
-        }
-        if ((st = stage.alloc(n, &dro))) return st;
-        if (im_out && (st = stage.alloc(n, &dio))) return st;
-    }
-    GenericFftArgs A{};
-    A.re_in = dre;
-    A.im_in = dim;
-    A.n = n;
-    A.log2n = ilog2(n);
-    A.dir = dir;
-    A.tw = tw;
-    A.scale = (float)(1.0 / std::sqrt((double)n));
-    A.re_out = dro;
-    A.im_out = dio;
+    Stage stage(ex);
+    GenericFftArgs A = fft_args(tw, n, dir);
+    A.re_in = stage.in(re_in, n);
+    A.im_in = im_in ? stage.in(im_in, n) : nullptr;
+    A.re_out = stage.out(re_out, n);
+    A.im_out = im_out ? stage.out(im_out, n) : nullptr;
     A.mode = im_out ? 0 : 1;
+    if (stage.status) return stage.status;
     if ((st = launch_fft_generic(A, 1, 1, s))) return st;
-    if (host_mode(ex)) {
-        DSPB_HIP(hipMemcpyAsync(re_out, dro, n * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (im_out)
-            DSPB_HIP(hipMemcpyAsync(im_out, dio, n * sizeof(float), hipMemcpyDeviceToHost, s));
-    }
-    return finish(ex);
+    return (st = stage.copy_back()) ? st : finish(ex);
 }
 
 int dsp_fft_forward(const float *in, float *re, float *im, uint32_t n, const dsp_exec *ex) {
@@ -1805,37 +1580,30 @@ int dsp_wav_decode(const void *payload, const dsp_wav_info *info, uint64_t frame
     if (frame0 > info->frames || frames > info->frames - frame0) return invalid("frame range past the payload");
     if (frames == 0) return DSP_OK;
     if (!payload || !out) return invalid("NULL buffer");
-    for (uint32_t c = 0; c < C; ++c)
-        if (!out[c]) return invalid("out[%u] is NULL", c);
+    int st;
+    if ((st = check_rows("out", out, C))) return st;
     DeviceGuard g(ex);
     if (g.status) return g.status;
     hipStream_t s = stream_of(ex);
     const uint64_t ba = (uint64_t)C * (info->bits_per_sample / 8u);
     const uint8_t *src = (const uint8_t *)payload;
     uint64_t f0 = frame0;
-    ChanOut o{};
-    Staged stage;
-    if (host_mode(ex)) {
-        float *d;
-        int st = stage.alloc((frames * ba + 3) / 4, &d);
-        if (st) return st;
-        DSPB_HIP(hipMemcpyAsync(d, src + frame0 * ba, frames * ba, hipMemcpyHostToDevice, s));
-        src = (const uint8_t *)d;
+    Stage stage(ex);
+    if (stage.host) {  // only the frames of the call are staged
+        src = (const uint8_t *)stage.in_bytes(src + frame0 * ba, frames * ba);
         f0 = 0;
-        for (uint32_t c = 0; c < C; ++c)
-            if ((st = stage.alloc(frames, &o.p[c]))) return st;
-    } else {
-        for (uint32_t c = 0; c < C; ++c) o.p[c] = out[c];
     }
+    ChanOut o{};
     bool al = true;
-    for (uint32_t c = 0; c < C; ++c) al = al && aligned(o.p[c], 16);
-    int st = launch_wav_decode(src, C, info->bits_per_sample, info->format == DSP_WAV_FORMAT_FLOAT, f0,
-                               frames, o, al, s);
-    if (st) return st;
-    if (host_mode(ex))
-        for (uint32_t c = 0; c < C; ++c)
-            DSPB_HIP(hipMemcpyAsync(out[c], o.p[c], frames * sizeof(float), hipMemcpyDeviceToHost, s));
-    return finish(ex);
+    for (uint32_t c = 0; c < C; ++c) {
+        o.p[c] = stage.out(out[c], frames);
+        al = al && aligned(o.p[c], 16);
+    }
+    if (stage.status) return stage.status;
+    if ((st = launch_wav_decode(src, C, info->bits_per_sample, info->format == DSP_WAV_FORMAT_FLOAT, f0, frames, o,
+                                al, s)))
+        return st;
+    return (st = stage.copy_back()) ? st : finish(ex);
 }
 
 int dsp_wav_encode(const float *const *in, uint32_t C, uint64_t frames, uint16_t format, uint16_t bits,
@@ -1844,31 +1612,18 @@ int dsp_wav_encode(const float *const *in, uint32_t C, uint64_t frames, uint16_t
     if (C == 0 || C > (uint32_t)kMaxChannels) return invalid("channels must be 1..%d", kMaxChannels);
     if (frames == 0) return DSP_OK;
     if (!in || !payload) return invalid("NULL buffer");
-    for (uint32_t c = 0; c < C; ++c)
-        if (!in[c]) return invalid("in[%u] is NULL", c);
+    int st;
+    if ((st = check_rows("in", in, C))) return st;
     DeviceGuard g(ex);
     if (g.status) return g.status;
     hipStream_t s = stream_of(ex);
-    const uint64_t bytes = frames * C * (bits / 8u);
-    uint8_t *dst = (uint8_t *)payload;
+    Stage stage(ex);
+    uint8_t *dst = (uint8_t *)stage.out_bytes(payload, frames * C * (bits / 8u));
     ChanOut i{};
-    Staged stage;
-    if (host_mode(ex)) {
-        float *d;
-        int st = stage.alloc((bytes + 3) / 4, &d);
-        if (st) return st;
-        dst = (uint8_t *)d;
-        for (uint32_t c = 0; c < C; ++c) {
-            if ((st = stage.alloc(frames, &i.p[c]))) return st;
-            DSPB_HIP(hipMemcpyAsync(i.p[c], in[c], frames * sizeof(float), hipMemcpyHostToDevice, s));
-        }
-    } else {
-        for (uint32_t c = 0; c < C; ++c) i.p[c] = const_cast<float *>(in[c]);
-    }
-    int st = launch_wav_encode(dst, C, bits, format == DSP_WAV_FORMAT_FLOAT, frames, i, s);
-    if (st) return st;
-    if (host_mode(ex)) DSPB_HIP(hipMemcpyAsync(payload, dst, bytes, hipMemcpyDeviceToHost, s));
-    return finish(ex);
+    for (uint32_t c = 0; c < C; ++c) i.p[c] = const_cast<float *>(stage.in(in[c], frames));
+    if (stage.status) return stage.status;
+    if ((st = launch_wav_encode(dst, C, bits, format == DSP_WAV_FORMAT_FLOAT, frames, i, s))) return st;
+    return (st = stage.copy_back()) ? st : finish(ex);
 }
 
 // ---------------------------------------------------------------------------
@@ -1882,24 +1637,13 @@ int dsp_minmax_decimate(const float *x, uint64_t n, uint32_t pixels, float *vmax
     DeviceGuard g(ex);
     if (g.status) return g.status;
     hipStream_t s = stream_of(ex);
-    const float *dx = x;
-    float *dmax = vmax, *dmin = vmin;
-    Staged stage;
-    if (host_mode(ex)) {
-        float *t;
-        int st;
-        if ((st = stage.alloc(n, &t))) return st;
-        if (n) DSPB_HIP(hipMemcpyAsync(t, x, n * sizeof(float), hipMemcpyHostToDevice, s));
-        dx = t;
-        if ((st = stage.alloc(pixels, &dmax)) || (st = stage.alloc(pixels, &dmin))) return st;
-    }
+    Stage stage(ex);
+    const float *dx = stage.in(x, n);
+    float *dmax = stage.out(vmax, pixels), *dmin = stage.out(vmin, pixels);
+    if (stage.status) return stage.status;
     int st = launch_minmax(dx, n, pixels, dmax, dmin, s);
     if (st) return st;
-    if (host_mode(ex)) {
-        DSPB_HIP(hipMemcpyAsync(vmax, dmax, pixels * sizeof(float), hipMemcpyDeviceToHost, s));
-        DSPB_HIP(hipMemcpyAsync(vmin, dmin, pixels * sizeof(float), hipMemcpyDeviceToHost, s));
-    }
-    return finish(ex);
+    return (st = stage.copy_back()) ? st : finish(ex);
 }
 
 int dsp_spectrogram_decimate(const float *mag, uint64_t F, uint32_t K, uint64_t ld, uint32_t pixels,
@@ -1911,23 +1655,13 @@ int dsp_spectrogram_decimate(const float *mag, uint64_t F, uint32_t K, uint64_t 
     DeviceGuard g(ex);
     if (g.status) return g.status;
     hipStream_t s = stream_of(ex);
-    const float *dm = mag;
-    float *dout = out;
-    Staged stage;
-    if (host_mode(ex)) {
-        float *t;
-        int st;
-        const uint64_t nin = F ? (F - 1) * ld + K : 0;
-        if ((st = stage.alloc(nin, &t))) return st;
-        if (nin) DSPB_HIP(hipMemcpyAsync(t, mag, nin * sizeof(float), hipMemcpyHostToDevice, s));
-        dm = t;
-        if ((st = stage.alloc((uint64_t)pixels * K, &dout))) return st;
-    }
+    Stage stage(ex);
+    const float *dm = stage.in(mag, F ? (F - 1) * ld + K : 0);  // the last row ends at its K-th bin
+    float *dout = stage.out(out, (uint64_t)pixels * K);
+    if (stage.status) return stage.status;
     int st = launch_spectro(dm, F, K, ld, pixels, dout, s);
     if (st) return st;
-    if (host_mode(ex))
-        DSPB_HIP(hipMemcpyAsync(out, dout, (uint64_t)pixels * K * sizeof(float), hipMemcpyDeviceToHost, s));
-    return finish(ex);
+    return (st = stage.copy_back()) ? st : finish(ex);
 }
 
 }  // extern "C"

@@ -272,7 +272,7 @@ def test_pk_ramp_table_periods(torch_cuda, oracle, B):
                                          (-0.25, 3e-9, 256),   # not exact
                                          (0.9, 0.002, 384)])   # non-pow2 B: table path
 def test_ir_ramp_closed_form_and_table(torch_cuda, oracle, gain, step, B):
-    """capi.cpp ramp_closed_form: IR_test's block table is evaluated in
+    """host_tables.cpp ramp_closed_form: IR_test's block table is evaluated in
     closed form only when the sequential f64 recurrence is exact; either
     way the render is bit-identical to the reference callback."""
     n = 8192 * 3 + 1000
