@@ -15,6 +15,10 @@
 //     --plugin NAME     gain_test (default) | IR_test | no_op | static_gain |
 //                       PATH.cpp (any reference-style plugin source, compiled
 //                       for gfx950 at run time: DSP_PLUGIN_GENERIC)
+//     --convolve IR.wav convolve with an impulse response (DSP_PLUGIN_CONV): the
+//                       first channel of IR.wav (1..2^20 frames, decoded like the
+//                       input) is the taps for every device channel.  Not with
+//                       --plugin
 //     --gain G          gain_test / static_gain gain (0.2 / 0.1)
 //     --ir G,STEP       IR_test parameters (0.9,0.002)
 //     --block B         block size (512)
@@ -94,7 +98,7 @@ bool read_file(const char *path, std::vector<unsigned char> &out) {
 void usage() {
     std::fprintf(stderr,
                  "usage: dspbench_render IN.wav OUT.wav [--plugin gain_test|IR_test|no_op|static_gain|PATH.cpp]\n"
-                 "       [--gain G] [--ir G,STEP] [--block B] [--bits 16|24|32|float] [--stft MAG.f32]"
+                 "       [--convolve IR.wav] [--gain G] [--ir G,STEP] [--block B] [--bits 16|24|32|float] [--stft MAG.f32]"
                  " [--device N]\n"
                  "       [--device-channels C] [--device-rate R] [--loop NBLOCKS]\n"
                  "       [--world W --rank R --comm-id FILE [--run-id STR] [--chunk SAMPLES]]\n");
@@ -147,7 +151,8 @@ int main(int argc, char **argv) {
         return 2;
     }
     const char *in_path = argv[1], *out_path = argv[2];
-    std::string plugin = "gain_test", stft_path, bits_opt;
+    std::string plugin = "gain_test", stft_path, bits_opt, conv_path;
+    bool have_plugin = false;
     float gain = -1.f, ir_gain = 0.9f, ir_step = 0.002f;
     uint32_t B = 512;
     int device = -1;
@@ -165,7 +170,8 @@ int main(int argc, char **argv) {
             usage();
             return 2;
         }
-        if (a == "--plugin") plugin = v;
+        if (a == "--plugin") plugin = v, have_plugin = true;
+        else if (a == "--convolve") conv_path = v;
         else if (a == "--gain") gain = std::strtof(v, nullptr);
         else if (a == "--ir") {
             if (std::sscanf(v, "%f,%f", &ir_gain, &ir_step) != 2) {
@@ -191,6 +197,10 @@ int main(int argc, char **argv) {
     }
     if (B == 0) {
         usage();
+        return 2;
+    }
+    if (have_plugin && !conv_path.empty()) {
+        std::fprintf(stderr, "dspbench_render: --convolve and --plugin exclude each other\n");
         return 2;
     }
     const bool multi = !comm_path.empty();
@@ -258,7 +268,38 @@ int main(int argc, char **argv) {
     float pv[2] = {0.f, 0.f};
     dsp_module *mod = nullptr;
     std::vector<unsigned char> gparams;
-    if (plugin == "gain_test") {
+    std::vector<float> taps;
+    if (!conv_path.empty()) {  // the IR file's first channel, through the same parse + GPU decode
+        std::vector<unsigned char> irf;
+        if (!read_file(conv_path.c_str(), irf)) {
+            std::fprintf(stderr, "dspbench_render: cannot read %s\n", conv_path.c_str());
+            return 1;
+        }
+        dsp_wav_info ii{};
+        if ((st = dsp_wav_parse(irf.data(), irf.size(), &ii))) return fail("dsp_wav_parse (impulse response)", st);
+        if (ii.frames == 0 || ii.frames > (1u << 20) || ii.channels == 0 || ii.channels > 16) {
+            std::fprintf(stderr, "dspbench_render: %s: %llu frames, %u channels (1..2^20 frames, 1..16 channels)\n",
+                         conv_path.c_str(), (unsigned long long)ii.frames, ii.channels);
+            return 1;
+        }
+        std::vector<unsigned char> irp(ii.data_bytes);
+        for (uint64_t c = 0, o = 0; c < ii.n_data_chunks; ++c) {
+            std::memcpy(irp.data() + o, irf.data() + ii.data_offset[c], ii.data_size[c]);
+            o += ii.data_size[c];
+        }
+        void *d_ir = nullptr;
+        HIPCK(hipMalloc(&d_ir, irp.size() + 16));
+        HIPCK(hipMemcpyAsync(d_ir, irp.data(), irp.size(), hipMemcpyHostToDevice, s));
+        std::vector<float *> dir(ii.channels);
+        for (uint32_t c = 0; c < ii.channels; ++c) HIPCK(hipMalloc(&dir[c], ii.frames * sizeof(float)));
+        if ((st = dsp_wav_decode(d_ir, &ii, 0, ii.frames, dir.data(), &ex))) return fail("dsp_wav_decode", st);
+        taps.resize(ii.frames);
+        HIPCK(hipMemcpyAsync(taps.data(), dir[0], ii.frames * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIPCK(hipStreamSynchronize(s));
+        for (float *q : dir) HIPCK(hipFree(q));
+        HIPCK(hipFree(d_ir));
+        p.kind = DSP_PLUGIN_CONV, p.params = taps.data(), p.params_size = (uint32_t)(taps.size() * sizeof(float));
+    } else if (plugin == "gain_test") {
         pv[0] = gain >= 0.f ? gain : 0.2f;  // build/gain_test.cpp:23
         p.kind = DSP_PLUGIN_GAIN, p.params = pv, p.params_size = 4;
     } else if (plugin == "static_gain") {

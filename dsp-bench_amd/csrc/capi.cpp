@@ -79,6 +79,7 @@ struct CachedTable {
     DevTable dev;
     float h2048r = 0.f, h2048i = 0.f;  // FIR: H[2048] of the 8192-point spectrum
     uint32_t window = 0;               // BIQUAD: biquad_tables' W
+    size_t bytes = 0;                  // of the device table
 };
 typedef std::vector<CachedTable> TableCache;  // oldest first
 
@@ -98,6 +99,7 @@ struct DeviceRes {
     std::map<std::pair<void *, int>, std::pair<float *, size_t>> scratch;  // per (stream, slot)
     TableCache fir;                                            // FIR filters seen (plugin_map)
     TableCache iir;                                            // biquad cascades seen (plugin_map)
+    TableCache conv;                                           // CONV impulse responses seen (plugin_map)
     std::map<void *, IirWork> iir_work;                        // per stream
     uint32_t *iir_fb_host = nullptr, *iir_fb_dev = nullptr;  // host-mapped counter of repaired launches
     float *delta = nullptr;  // 2048 floats: 1, 0, 0, ... (compute_IR's impulse, read-only)
@@ -283,7 +285,7 @@ static int set_wincomp(int dev, hipStream_t s, int kind, Stft8kArgs *A) {
 
 // Stream-ordered scratch: calls on one stream are serialised by the stream,
 // so one buffer per (device, stream, slot) is enough.  Slots: 0 the IR_test
-// block table, 1 loop mode's wrapped file.
+// block table, 1 loop mode's wrapped file, 2 a CONV channel group's spectra.
 static int get_scratch(int dev, hipStream_t s, size_t bytes, float **out, int slot_id = 0) {
     std::lock_guard<std::mutex> lk(g_mu);
     DeviceRes &r = g_res[dev];
@@ -444,13 +446,19 @@ static int iir_launch(int dev, hipStream_t s, BiquadArgs *A, uint32_t sections, 
     return DSP_OK;
 }
 
-// The entry of `key` in a cache of at most 8 device tables, with g_mu held.
+// device bytes of CONV tables a device keeps cached beside the newest one (a
+// 2^20-tap table is 8.25 MiB)
+constexpr size_t kConvCacheBytes = 64u << 20;
+
+// The entry of `key` in a cache of at most 8 device tables -- and, with
+// max_bytes set, of at most that many bytes of them beside the newest, the
+// oldest leaving first -- with g_mu held.
 // On a miss build(h, entry) fills the host table and the entry's payload; the
 // table is uploaded once per key, not once per render.  The caller copies
 // what it needs out of *out (the DevTable as its hold) before it unlocks.
 template <class Build>
 static int cached_table(TableCache &cache, const std::vector<float> &key, int dev, hipStream_t s, const char *what,
-                        Build build, const CachedTable **out) {
+                        Build build, const CachedTable **out, size_t max_bytes = 0) {
     for (auto &e : cache)
         if (e.key == key) { *out = &e; return DSP_OK; }
     CachedTable e;
@@ -459,6 +467,7 @@ static int cached_table(TableCache &cache, const std::vector<float> &key, int de
     const int st = first_use_table(d, s, what, [&] {
         std::vector<float> h;
         build(h, e);
+        e.bytes = h.size() * sizeof(float);
         return h;
     });
     if (st) return st;
@@ -467,6 +476,14 @@ static int cached_table(TableCache &cache, const std::vector<float> &key, int de
     // unless a call still holds it -- dev_table's deleter waits for the device
     // with g_mu held (ADVICE.md's open finding)
     if (cache.size() >= 8) cache.erase(cache.begin());
+    if (max_bytes) {
+        size_t held = e.bytes;
+        for (auto &c : cache) held += c.bytes;
+        while (!cache.empty() && held > max_bytes) {
+            held -= cache.front().bytes;
+            cache.erase(cache.begin());
+        }
+    }
     cache.push_back(std::move(e));
     *out = &cache.back();
     return DSP_OK;
@@ -484,6 +501,8 @@ static int plugin_map(const dsp_plugin *p, uint32_t B, int dev, hipStream_t s, S
     m->b_mask = is_pow2(B) ? B - 1 : 0;
     m->taps = nullptr;
     m->ntaps8 = 0;
+    m->convH = nullptr;
+    m->conv_parts = 0;
     m->iir_tab = nullptr;
     m->sections = 0;
     m->iir_window = 0;
@@ -566,6 +585,32 @@ static int plugin_map(const dsp_plugin *p, uint32_t B, int dev, hipStream_t s, S
         m->pairH = tp + T8 + 8196;  // 16-byte aligned: T8 and 8196 are multiples of 4
         m->olsH2048[0] = h2048[0];
         m->olsH2048[1] = h2048[1];
+        return DSP_OK;
+    }
+    case DSP_PLUGIN_CONV: {  // build-defined: Parameters{float taps[T]}, a long impulse response
+        const uint32_t T = p->params_size / 4;
+        if (!p->params || T == 0 || p->params_size % 4 || T > kConvMaxTaps)
+            return invalid("CONV plugin needs 1..%u float taps as its params blob", kConvMaxTaps);
+        std::vector<float> key((const float *)p->params, (const float *)p->params + T);
+        for (float v : key)
+            if (!std::isfinite(v)) return invalid("CONV taps must be finite");
+        uint32_t parts = 0;
+        if (conv_plan(T, 0, 1, 1, &parts, nullptr, nullptr)) return invalid("CONV plugin: bad tap count");
+        {
+            std::lock_guard<std::mutex> lk(g_mu);
+            const CachedTable *ct = nullptr;
+            const int st = cached_table(g_res[dev].conv, key, dev, s, "a CONV impulse response's partition spectra",
+                                        [&](std::vector<float> &h, CachedTable &) {
+                h.assign((size_t)parts * 4 * kConvSpec4, 0.f);
+                conv_table(key.data(), T, h.data());
+            }, &ct, kConvCacheBytes);
+            if (st) return st;
+            *table = ct->dev;  // held by the call (copied under the lock)
+        }
+        m->kind = MapKind::Conv;
+        m->convH = table->get();
+        m->conv_parts = parts;
+        m->ntaps = T;
         return DSP_OK;
     }
     case DSP_PLUGIN_BIQUAD: {  // build-defined: Parameters{float coef[5 S]}, S = 1..4 sections
@@ -925,6 +970,34 @@ static int render_device(const float *const *in, uint32_t in_ch, uint64_t L, flo
             });
         });
     }
+    if (map.kind == MapKind::Conv) {  // partitioned convolution from the start of the file
+        if (start != 0 || goff != 0) return invalid("CONV render: whole files only (sample_offset 0)");
+        if (rows_overlap(in, std::min(in_ch, C), L, out, C, end))
+            return invalid("CONV render: output rows overlap input rows (a frame's input is read after its "
+                           "neighbour's output is written)");
+        const v2f *tw = nullptr;
+        int dev = 0;
+        DSPB_HIP(hipGetDevice(&dev));
+        if (int st = get_tw(dev, s, &tw)) return st;
+        // sized by dsp_conv_plan's own function: one channel group's spectra
+        uint64_t F = 0, scratch_bytes = 0;
+        if (const char *why = conv_plan(map.ntaps, L, B, C, nullptr, &F, &scratch_bytes)) return invalid("%s", why);
+        float *scratch = nullptr;
+        if (int st = get_scratch(dev, s, scratch_bytes, &scratch, 2)) return st;
+        return for_groups(C, [&](uint32_t c0, uint32_t cn) {
+            ConvArgs A{};
+            fill_rows(in, in_ch, out, c0, cn, &A.in, &A.in_ch, &A.out);
+            A.L = L;
+            A.Ly = end;
+            A.F = F;
+            A.H = reinterpret_cast<const float4 *>(map.convH);
+            A.parts = map.conv_parts;
+            A.X = reinterpret_cast<float4 *>(scratch);
+            A.Y = A.X + (uint64_t)cn * F * kConvSpec4;
+            A.tw = tw;
+            return launch_conv(A, cn, s);
+        });
+    }
     if (map.kind == MapKind::Fir) {  // convolution from the start of the file
         if (start != 0 || goff != 0) return invalid("FIR render: whole files only (sample_offset 0)");
         if (map.ntaps <= 1025 && !map.fir_direct) {
@@ -1187,6 +1260,12 @@ int dsp_biquad_plan(const float *coef, uint32_t sections, uint32_t *window) {
     return DSP_OK;
 }
 
+int dsp_conv_plan(uint32_t taps, uint64_t L, uint32_t B, uint32_t C, uint32_t *partitions, uint64_t *frames,
+                  uint64_t *scratch_bytes) {
+    if (const char *why = conv_plan(taps, L, B, C, partitions, frames, scratch_bytes)) return invalid("%s", why);
+    return DSP_OK;
+}
+
 uint64_t dsp_stft_frame_count(uint64_t L, uint32_t N, uint32_t H) {
     if (N == 0 || H == 0 || L < N) return 0;
     return (L - N) / H + 1;
@@ -1277,7 +1356,7 @@ int dsp_render_loop(const float *const *in, uint32_t in_channels, uint64_t L, ui
     if (map.kind == MapKind::Noop || map.kind == MapKind::Gain || map.kind == MapKind::Ramp ||
         map.kind == MapKind::GainTable)
         return (st = wrap(in, out, C, map)) ? st : finish(ex);
-    // FIR / GENERIC: the wrapped file is materialised (the plugin's block
+    // FIR / CONV / GENERIC: the wrapped file is materialised (the plugin's block
     // stream), then rendered as a one-shot file of nblocks B samples
     float *tmp = nullptr;
     if (in_ch) {
@@ -1352,7 +1431,8 @@ int dsp_render_stft(const float *const *in, uint32_t in_channels, uint64_t L,
     set_result(ex, by_class(orig.kind, map.kind) ? DSP_RESULT_CLASS : 0u);
 
     bool fused = (N == 8192) && (H % 128 == 0) && (H <= N) && (goff % 2 == 0) && F > 0 &&
-                 map.kind != MapKind::Fir && map.kind != MapKind::Generic && map.kind != MapKind::Biquad;
+                 map.kind != MapKind::Fir && map.kind != MapKind::Generic && map.kind != MapKind::Biquad &&
+                 map.kind != MapKind::Conv;
     for (uint32_t c = 0; c < C; ++c) fused = fused && aligned(dout[c], 8);
     for (uint32_t c = 0; c < in_channels; ++c) fused = fused && aligned(din[c], 8);
 

@@ -22,7 +22,7 @@ struct ChanOut {
 // `table` is the IR_test ramp (B floats) computed on the device by
 // ramp_table_kernel, or (GainTable) C rows of B gains, a GENERIC plugin's
 // per-(channel, position) gains; Gain uses the scalar `a`.
-enum class MapKind : int { Noop = 0, Gain = 1, Ramp = 3, Fir = 4, Generic = 5, Biquad = 6, GainTable = 7 };
+enum class MapKind : int { Noop = 0, Gain = 1, Ramp = 3, Fir = 4, Generic = 5, Biquad = 6, GainTable = 7, Conv = 8 };
 
 struct SampleMap {
     MapKind kind;
@@ -37,6 +37,8 @@ struct SampleMap {
     const float *olsH;   // Fir: FFT(taps)/16384 in fir_fft.hip's lane-major pair layout
     float olsH2048[2];   // Fir: H[2048]/16384
     const float *pairH;  // Fir: FFT_4096(taps)/4096 in fir_pair_kernel's layout (fir_fft.hip)
+    const float *convH;  // Conv: conv_parts partition spectra (host_tables.cpp conv_table)
+    uint32_t conv_parts; // Conv: ceil(taps / 4096); ntaps holds the tap count
     const float *iir_tab; // Biquad: [5 S coefficients, padded to 20][M^(T l), l <= 64][M^(64 T k), k <= 256]
     uint32_t sections;   // Biquad: S (1..4)
     uint32_t iir_window; // Biquad: tiles of aggregates that reach a tile's state (0: inclusive look-back)

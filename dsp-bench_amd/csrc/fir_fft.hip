@@ -18,31 +18,12 @@
 //             the render is written once)
 //
 // tools/olsave_model.py is the numpy model of exactly this index math.
-#include "fft_pk.hpp"
+#include "ols_frame.hpp"
 
 namespace dspb {
 
 constexpr uint32_t kOlsHop = 7168;    // outputs per frame
 constexpr uint32_t kOlsHist = 1024;   // history samples per frame (T - 1 <= 1024)
-
-// twiddles for the 4096-point passes; `salt` is an opaque zero so that the
-// second load (for the inverse) is not merged with the first and the
-// compiler does not keep 30 VGPRs of twiddles live across the whole frame
-__device__ __forceinline__ void load_stage_tw(const v2f *tw, uint32_t lane, uint32_t salt, cx (&tlo)[8],
-                                              cx2 (&thp)[4]) {
-    const v2f *t = tw + salt;
-#pragma unroll
-    for (int j = 1; j < 8; ++j) {
-        const v2f a = (t + 8192u + 64u * (uint32_t)(j - 1))[lane];
-        tlo[j] = cx{a.x, a.y};
-    }
-    const float4 *tp4 = reinterpret_cast<const float4 *>(t + 8192u + 896u);
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-        const float4 q = tp4[64u * (uint32_t)h + lane];
-        thp[h] = cx2{v2f{q.x, q.y}, v2f{q.z, q.w}};
-    }
-}
 
 // EDGE: frames that reach before sample 0 or past L (bounds-checked loads);
 // interior frames run the EDGE = false instantiation
@@ -59,40 +40,13 @@ __device__ __forceinline__ void fir_fft_frame(const FirFftArgs &A, uint64_t f, u
 
     // ---- frame: v[b] = (x[fs + 2l + 128b], x[fs + 2l + 128b + 1]), zero outside [0, L)
     cx2 P[32];
-    {
-        cx v[64];
-        if constexpr (!EDGE) {
-            if (x != nullptr) {
-#pragma unroll
-                for (int b = 0; b < 64; ++b) {
-                    const v2f t = reinterpret_cast<const v2f *>(x + fs + 128 * b)[lane];
-                    v[b] = cx{t.x, t.y};
-                }
-            } else {  // a channel the file does not have: silence
-#pragma unroll
-                for (int b = 0; b < 64; ++b) v[b] = cx{0.f, 0.f};
-            }
-        } else {
-#pragma unroll
-            for (int b = 0; b < 64; ++b) {
-                const int64_t s = fs + 2 * (int64_t)lane + 128 * b;
-                v[b] = cx{(x && s >= 0 && (uint64_t)s < A.L) ? x[s] : 0.f,
-                          (x && s + 1 >= 0 && (uint64_t)(s + 1) < A.L) ? x[s + 1] : 0.f};
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 32; ++j)
-            P[j] = cx2{v2f{v[2 * j].r, v[2 * j + 1].r}, v2f{v[2 * j].i, v[2 * j + 1].i}};
-    }
+    ols_load_frame<EDGE>(x, fs, A.L, lane, P);
 
     cx zp[32], zm[32];
     fft4096_pk<false, false, false, true>(P, lds, tlo, thp, lane, zp, zm);
 
     // ---- split, H multiply, inverse split, paired over (ka, ka + 16) --------
-    const uint32_t src = ((64u - lane) & 63u) * 4u;
-    const bool l0 = lane == 0;
-    const v2f wl2 = A.tw[lane];  // W8192^l
-    const cx wl = cx{wl2.x, wl2.y};
+    const OlsLane ln = ols_lane(A.tw, lane);
     // own Z'[l + 64 ka] (ka < 32) and, received from lane 64 - l, Z'[l + 64 ka']
     // (ka' = 32 + q): lane 64 - l computes it as its Z'[M - k] at ka = 31 - q
     // and it is sent in the same iteration; lane 0 (which pairs with itself,
@@ -100,44 +54,25 @@ __device__ __forceinline__ void fir_fft_frame(const FirFftArgs &A, uint64_t f, u
     cx zk[32], zr[32];
 #pragma unroll
     for (int ka = 0; ka < 16; ++ka) {
-        const cx a0 = ka == 0 ? zp[0] : zm[32 - ka], b0 = zm[31 - ka];
-        const cx a1 = zm[16 - ka], b1 = zm[15 - ka];
-        const cx s0 = cx{l0 ? a0.r : b0.r, l0 ? a0.i : b0.i};
-        const cx s1 = cx{l0 ? a1.r : b1.r, l0 ? a1.i : b1.i};
-        const cx2 Pp = cx2{v2f{bperm(src, s0.r), bperm(src, s1.r)}, v2f{bperm(src, s0.i), bperm(src, s1.i)}};
-        const cx2 Z = cx2{v2f{zp[ka].r, zp[ka + 16].r}, v2f{zp[ka].i, zp[ka + 16].i}};
-        const cx2 E = cx2{Z.r + Pp.r, Z.i - Pp.i};
-        const cx2 D = cx2{Z.r - Pp.r, Z.i + Pp.i};
-        const cx2 tw = cmulb(wl, cx2{v2f{kW128_re[ka], kW128_re[ka + 16]}, v2f{kW128_im[ka], kW128_im[ka + 16]}});
-        const cx2 T = cmul2(negi(D), tw);
-        const cx2 X1 = E + T;  // 2 X[k]
-        const cx2 X2 = E - T;  // conj 2 X[M - k]
+        const cx2 tw = ols_tw(ln, ka);
+        cx2 X1, X2;
+        ols_split(zp, zm, ka, ln, tw, X1, X2);
         const float4 ha = hs[(2u * ka) * 64u + lane], hb = hs[(2u * ka + 1u) * 64u + lane];
         const cx2 Hk = cx2{v2f{ha.x, ha.y}, v2f{ha.z, ha.w}};
         const cx2 HMk = cx2{v2f{hb.x, hb.y}, v2f{hb.z, hb.w}};
         const cx2 Yk = cmul2(X1, Hk);
         const cx2 YMk = cmul2(cx2{X2.r, -X2.i}, HMk);
-        const cx2 E2 = cx2{Yk.r + YMk.r, Yk.i - YMk.i};                           // Y[k] + conj Y[M-k]
-        const cx2 O2 = cmul2(cx2{Yk.r - YMk.r, Yk.i + YMk.i}, cx2{tw.r, -tw.i});  // (..) W^-k
-        const cx2 Zk = cx2{E2.r - O2.i, E2.i + O2.r};                            // E + i O
-        const cx2 ZMk = cx2{E2.r + O2.i, O2.r - E2.i};                           // conj E + i conj O
-        zk[ka] = cx{Zk.r.x, Zk.i.x};
-        zk[ka + 16] = cx{Zk.r.y, Zk.i.y};
-        zr[31 - ka] = cx{bperm(src, ZMk.r.x), bperm(src, ZMk.i.x)};
-        zr[15 - ka] = cx{bperm(src, ZMk.r.y), bperm(src, ZMk.i.y)};
+        ols_unsplit(Yk, YMk, tw, ka, ln, zk, zr);
     }
-    // lane 0 received its own Z'[M - k] of ka = 31 - q at q; it needs the one of
-    // ka = 32 - q, i.e. what landed at q - 1, and at q = 0 the self-paired
-    // bin k = 2048: Z[2048] = zm[0], 2 X[2048] = 2 conj Z, Z'[2048] = 2 conj Y
+    // bin 2048: Z[2048] = zm[0], 2 X[2048] = 2 conj Z
     {
         const cx Z = zm[0];
-        const cx Y = mulc(cx{2.f * Z.r, -2.f * Z.i}, A.h2048.x, A.h2048.y);
-#pragma unroll
-        for (int q = 31; q >= 1; --q) zr[q] = cx{l0 ? zr[q - 1].r : zr[q].r, l0 ? zr[q - 1].i : zr[q].i};
-        zr[0] = cx{l0 ? 2.f * Y.r : zr[0].r, l0 ? -2.f * Y.i : zr[0].i};
+        ols_unsplit_lane0(mulc(cx{2.f * Z.r, -2.f * Z.i}, A.h2048.x, A.h2048.y), ln, zr);
     }
 
     // ---- inverse 4096-point FFT over the register index ka -------------------
+    // (packed in place: as a helper taking zk / zr by reference this loop kept
+    // them in scratch memory)
     cx2 Q[32];
 #pragma unroll
     for (int j = 0; j < 32; ++j) {

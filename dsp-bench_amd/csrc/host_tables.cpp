@@ -74,6 +74,47 @@ void pair_table(const float *taps, uint32_t T, float *out) {
         }
 }
 
+// the partitioned table of conv_fdl.hip (DSP_PLUGIN_CONV): per partition p of
+// kConvHop taps, H_p = FFT_8192(partition zero-padded) / 16384 (the inverse's
+// 1/4096 and the two real-split halvings, as ols_table) in ols_table's pair
+// order as float4 [2 (64 ka + l) + h], then the padding slice: bin 2048 as
+// (re, 0, im, 0) and 63 zero float4
+void conv_table(const float *taps, uint32_t T, float *out) {
+    std::vector<double> re, im;
+    const double sc = 1.0 / 16384.0;
+    const uint32_t parts = (T + kConvHop - 1) / kConvHop;
+    for (uint32_t p = 0; p < parts; ++p) {
+        const uint32_t t0 = p * kConvHop;
+        taps_spectrum(taps + t0, std::min(kConvHop, T - t0), 8192, re, im);
+        float *sp = out + (size_t)p * 4 * kConvSpec4;
+        for (int ka = 0; ka < 16; ++ka)
+            for (int l = 0; l < 64; ++l) {
+                const int k1 = l + 64 * ka, k2 = k1 + 1024, m1 = 4096 - k1, m2 = 4096 - k2;
+                float *o = sp + 8 * (64 * ka + l);
+                o[0] = (float)(re[k1] * sc); o[1] = (float)(re[k2] * sc);
+                o[2] = (float)(im[k1] * sc); o[3] = (float)(im[k2] * sc);
+                o[4] = (float)(re[m1] * sc); o[5] = (float)(re[m2] * sc);
+                o[6] = (float)(im[m1] * sc); o[7] = (float)(im[m2] * sc);
+            }
+        float *pad = sp + 4 * 2048;
+        std::fill(pad, pad + 4 * 64, 0.f);
+        pad[0] = (float)(re[2048] * sc);
+        pad[2] = (float)(im[2048] * sc);
+    }
+}
+
+const char *conv_plan(uint32_t taps, uint64_t L, uint32_t B, uint32_t C, uint32_t *partitions, uint64_t *frames,
+                      uint64_t *scratch_bytes) {
+    if (taps == 0 || taps > kConvMaxTaps) return "DSP_PLUGIN_CONV: 1..2^20 taps";
+    if (B == 0) return "block size B must be > 0";
+    if (L > (1ull << 48)) return "DSP_PLUGIN_CONV: L > 2^48";
+    const uint64_t F = ((L + B - 1) / B * B + kConvHop - 1) / kConvHop;
+    if (partitions) *partitions = (taps + kConvHop - 1) / kConvHop;
+    if (frames) *frames = F;
+    if (scratch_bytes) *scratch_bytes = 2 * (uint64_t)std::min<uint32_t>(C, 16) * F * kConvSpec4 * 16;
+    return nullptr;
+}
+
 // IR_test (build/IR_test.cpp:47-58) runs `gain -= step` in double from the
 // float parameters.  The sequence is often exact -- every partial result a
 // double -- and then table[i] = (float)(gain - i step) is one f64 FMA, with

@@ -2,6 +2,7 @@
 // translation units and the C ABI (capi.cpp).
 #pragma once
 #include "common.hpp"
+#include "host_tables.hpp"  // kConvHop, kConvSpec4
 
 struct dsp_module;  // include/dspbench/module.h
 
@@ -119,6 +120,23 @@ constexpr uint32_t kPairHop = 3072;
 int launch_fir_pair(const FirFftArgs &A, uint32_t C, hipStream_t s);
 int launch_fir(const float *x, uint64_t L, float *y, uint64_t Ly, const float *h8, uint32_t T8,
                bool y_aligned16, hipStream_t s);
+// DSP_PLUGIN_CONV (conv_fdl.hip): partitioned overlap-save, 8192-point real
+// frames of hop kConvHop, one launch_conv per channel group: forward
+// transforms into X, the multiply-accumulate over partitions into Y, inverse
+// transforms into the render rows
+struct ConvArgs {
+    ChanIn in;           // input channels
+    uint32_t in_ch;
+    uint64_t L;          // input samples (zero past)
+    ChanOut out;         // render rows, Ly samples
+    uint64_t Ly;
+    uint64_t F;          // frames = ceil(Ly / kConvHop)
+    const float4 *H;     // `parts` spectra of kConvSpec4 float4 (host_tables.cpp conv_table)
+    uint32_t parts;      // partitions = ceil(T / kConvHop)
+    float4 *X, *Y;       // scratch: [channel][frame] spectra of the input and of the output
+    const v2f *tw;       // T8192 + lane-major stage twiddles (capi.cpp get_tw)
+};
+int launch_conv(const ConvArgs &A, uint32_t C, hipStream_t s);
 // DSP_PLUGIN_BIQUAD (iir.hip): one launch renders C <= 16 channels of Ly
 // samples from zero state; tiles of 64 lanes x biquad_lane_samples() samples
 struct BiquadArgs {

@@ -656,10 +656,10 @@ int dsp_render_stft_sharded(const float *const *in, uint32_t in_channels, uint64
                        "State, which the reference carries from block to block (audio.cpp:160-165); shard it by "
                        "channel (DSP_SHARD_CHANNELS)");
     if (sh->mode == DSP_SHARD_TIME && sh->world > 1 && plugin &&
-        (plugin->kind == DSP_PLUGIN_FIR || plugin->kind == DSP_PLUGIN_BIQUAD))
+        (plugin->kind == DSP_PLUGIN_FIR || plugin->kind == DSP_PLUGIN_BIQUAD || plugin->kind == DSP_PLUGIN_CONV))
         return invalid("time sharding needs blocks that render independently: a %s filter's state runs through "
                        "the whole file; shard it by channel (DSP_SHARD_CHANNELS)",
-                       plugin->kind == DSP_PLUGIN_FIR ? "FIR" : "BIQUAD");
+                       plugin->kind == DSP_PLUGIN_FIR ? "FIR" : plugin->kind == DSP_PLUGIN_CONV ? "CONV" : "BIQUAD");
 
     int prev = -1;
     SH_HIP(hipGetDevice(&prev));

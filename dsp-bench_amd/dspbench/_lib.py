@@ -27,6 +27,7 @@ DSP_PLUGIN_STATIC_GAIN = 2
 DSP_PLUGIN_IR_RAMP = 3
 DSP_PLUGIN_FIR = 4
 DSP_PLUGIN_BIQUAD = 5
+DSP_PLUGIN_CONV = 6
 DSP_PLUGIN_GENERIC = 16
 
 DSP_EXEC_HOST_BUFFERS = 0x1
@@ -141,6 +142,8 @@ _SIGS = {
     "dsp_last_error": (C.c_char_p, []),
     "dsp_device_count": (C.c_int, []),
     "dsp_stft_frame_count": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32]),
+    "dsp_conv_plan": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
+                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "dsp_render_offline": (C.c_int, [FPP, C.c_uint32, C.c_uint64, FPP, C.c_uint32, C.c_uint32,
                                      C.c_float, C.POINTER(dsp_plugin), C.POINTER(dsp_exec)]),
     "dsp_render_loop": (C.c_int, [FPP, C.c_uint32, C.c_uint64, C.c_uint64, FPP, C.c_uint32, C.c_uint32,

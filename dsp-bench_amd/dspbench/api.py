@@ -74,6 +74,14 @@ class Plugin:
                       exec_flags=L.DSP_EXEC_FIR_DIRECT if direct else 0)
 
     @staticmethod
+    def conv(taps) -> "Plugin":
+        """Convolution with a long impulse response (DSP_PLUGIN_CONV): FIR's
+        semantics, y[n] = sum_k taps[k] x[n - k], for 1..2^20 finite taps, by
+        partitioned FFT overlap-save (conv_plan gives its sizes)."""
+        t = np.ascontiguousarray(np.asarray(taps, dtype=np.float32).reshape(-1))
+        return Plugin(L.DSP_PLUGIN_CONV, t.tobytes(), b"", f"conv{t.size}")
+
+    @staticmethod
     def biquad(sections) -> "Plugin":
         """Build-defined cascade of 1..4 direct-form-I biquads (DSP_PLUGIN_BIQUAD):
         `sections` = rows (b0, b1, b2, a1, a2), each y = b0 x + b1 x1 + b2 x2 -
@@ -138,6 +146,15 @@ def _alloc_like(ref, shape):
         import torch
         return torch.empty(shape, dtype=torch.float32, device=ref.device)
     return np.empty(shape, dtype=np.float32)
+
+
+def conv_plan(taps: int, L_: int, B: int, C_out: int) -> tuple[int, int, int]:
+    """DSP_PLUGIN_CONV's plan for `taps` taps over a call of L_ samples in blocks
+    of B on C_out channels (dsp_conv_plan, host only): (partitions, frames,
+    scratch bytes of one channel group)."""
+    p, f, b = C.c_uint32(), C.c_uint64(), C.c_uint64()
+    check(L.lib().dsp_conv_plan(taps, L_, B, C_out, C.byref(p), C.byref(f), C.byref(b)), "dsp_conv_plan")
+    return p.value, f.value, b.value
 
 
 def stft_frames(L_: int, N: int, H: int) -> int:

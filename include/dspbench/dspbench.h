@@ -80,6 +80,13 @@ enum dsp_plugin_kind {
                                    state carried across blocks: whole files only (sample_offset 0;
                                    shard by channel).  Block-parallel (a state scan), fp32 within a
                                    bound of float64, not bit-exact with a serial chain; not in graphs */
+    DSP_PLUGIN_CONV = 6,        /* build-defined: convolution with a long impulse response, FIR's
+                                   semantics y[n] = sum_k taps[k] x[n-k] for params = float taps[T],
+                                   1 <= T <= 2^20 (21.8 s at 48 kHz), finite; zero initial history
+                                   carried across blocks: whole files only (sample_offset 0; shard
+                                   by channel).  Uniform partitioned overlap-save on 8192-point
+                                   frames (dsp_conv_plan); fp32 within a bound of float64.  Output
+                                   rows must not overlap input rows (DSP_ERR_INVALID) */
     DSP_PLUGIN_GENERIC = 16     /* compiled audio_callback run on the GPU (module) */
 };
 
@@ -163,6 +170,16 @@ uint64_t dsp_stft_frame_count(uint64_t L, uint32_t N, uint32_t H);
  * that does not decay that fast (a chained look-back: within the same error
  * bound, not bitwise reproducible).  DSP_ERR_INVALID for a bad blob. */
 int dsp_biquad_plan(const float *coef, uint32_t sections, uint32_t *window);
+
+/* DSP_PLUGIN_CONV's plan (host only, no device): partitions of the filter,
+ * frames of the call, and the device scratch bytes one channel group needs.
+ * partitions = ceil(taps / 4096); frames = ceil(ceil(L / B) B / 4096);
+ * scratch_bytes = 2 min(C, 16) frames 33792 (the input's and the output's
+ * spectra; channel groups of 16 run one after another over the same scratch,
+ * which the render keeps per stream).  Any out pointer may be NULL.
+ * DSP_ERR_INVALID for taps = 0, taps > 2^20 or B = 0. */
+int dsp_conv_plan(uint32_t taps, uint64_t L, uint32_t B, uint32_t C,
+                  uint32_t *partitions, uint64_t *frames, uint64_t *scratch_bytes);
 
 /* Test hooks (not for production use).
  * DSP_DEBUG_BIQUAD_SPIN_LIMIT (set): the sleeps a DSP_PLUGIN_BIQUAD look-back
