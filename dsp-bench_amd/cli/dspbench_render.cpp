@@ -34,6 +34,14 @@
 //     --device-rate R   the sample rate handed to the plugin and written to the
 //                       output header (the reference ignores the WAV's own rate,
 //                       wav_reader.h:7-14).  Default: the file's.
+//     --rate R          convert the input from its header's rate to R on the GPU
+//                       before the render (dsp_resample, default quality); R is
+//                       the rate handed to the plugin and written to the output
+//                       header.  With --convolve the impulse response is
+//                       converted from its own header's rate to R and scaled by
+//                       ir_rate / R (the filter's DC gain is kept); it must still
+//                       be <= 2^20 taps.  Not with --device-rate, --loop or
+//                       --comm-id
 //     --loop NBLOCKS    loop mode (audio.cpp:100-132): NBLOCKS blocks from a
 //                       file that wraps around (no --stft)
 //   multi-GPU (cfg 5, shard.h): one process per GPU, channels sharded one
@@ -100,7 +108,7 @@ void usage() {
                  "usage: dspbench_render IN.wav OUT.wav [--plugin gain_test|IR_test|no_op|static_gain|PATH.cpp]\n"
                  "       [--convolve IR.wav] [--gain G] [--ir G,STEP] [--block B] [--bits 16|24|32|float] [--stft MAG.f32]"
                  " [--device N]\n"
-                 "       [--device-channels C] [--device-rate R] [--loop NBLOCKS]\n"
+                 "       [--device-channels C] [--device-rate R] [--rate R] [--loop NBLOCKS]\n"
                  "       [--world W --rank R --comm-id FILE [--run-id STR] [--chunk SAMPLES]]\n");
 }
 
@@ -156,7 +164,7 @@ int main(int argc, char **argv) {
     float gain = -1.f, ir_gain = 0.9f, ir_step = 0.002f;
     uint32_t B = 512;
     int device = -1;
-    uint32_t dev_channels = 0, dev_rate = 0, world = 0, rank = 0;
+    uint32_t dev_channels = 0, dev_rate = 0, conv_rate = 0, world = 0, rank = 0;
     uint64_t loop_blocks = 0, chunk = 16ull << 20;
     bool have_rank = false;
     std::string comm_path, run_id;
@@ -184,7 +192,13 @@ int main(int argc, char **argv) {
         else if (a == "--device") device = std::atoi(v);
         else if (a == "--device-channels") dev_channels = (uint32_t)std::strtoul(v, nullptr, 10);
         else if (a == "--device-rate") dev_rate = (uint32_t)std::strtoul(v, nullptr, 10);
-        else if (a == "--loop") loop_blocks = std::strtoull(v, nullptr, 10);
+        else if (a == "--rate") {
+            conv_rate = (uint32_t)std::strtoul(v, nullptr, 10);
+            if (conv_rate == 0) {
+                usage();
+                return 2;
+            }
+        } else if (a == "--loop") loop_blocks = std::strtoull(v, nullptr, 10);
         else if (a == "--world") world = (uint32_t)std::strtoul(v, nullptr, 10);
         else if (a == "--rank") rank = (uint32_t)std::strtoul(v, nullptr, 10), have_rank = true;
         else if (a == "--comm-id") comm_path = v;
@@ -204,6 +218,11 @@ int main(int argc, char **argv) {
         return 2;
     }
     const bool multi = !comm_path.empty();
+    if (conv_rate && (dev_rate || loop_blocks || multi || world)) {
+        std::fprintf(stderr, "dspbench_render: --rate excludes --device-rate, --loop and the multi-GPU modes\n");
+        usage();
+        return 2;
+    }
     if (multi) {  // torchrun-style environment when not given explicitly
         const char *ew = std::getenv("WORLD_SIZE"), *er = std::getenv("RANK");
         if (!world) world = ew ? (uint32_t)std::atoi(ew) : 1;
@@ -231,8 +250,8 @@ int main(int argc, char **argv) {
     const uint32_t Cf = info.channels;                // the file's channels
     const uint32_t C = dev_channels ? dev_channels : Cf;  // the device's (the render's)
     const uint32_t Cin = Cf < C ? Cf : C;             // channels_to_write (audio.cpp:66)
-    const uint32_t rate = dev_rate ? dev_rate : info.sample_rate;
-    const uint64_t L = info.frames;
+    const uint32_t rate = conv_rate ? conv_rate : dev_rate ? dev_rate : info.sample_rate;
+    uint64_t L = info.frames;  // (--rate: the converted length from the conversion on)
     if (Cf == 0 || Cf > 16 || C == 0 || C > 16) {
         std::fprintf(stderr, "dspbench_render: %u file / %u device channels (1..16 supported)\n", Cf, C);
         return 1;
@@ -257,11 +276,26 @@ int main(int argc, char **argv) {
     void *d_pay = nullptr;
     HIPCK(hipMalloc(&d_pay, payload.size() + 16));
     HIPCK(hipMemcpyAsync(d_pay, payload.data(), payload.size(), hipMemcpyHostToDevice, s));
-    const uint64_t nblocks = loop_blocks ? loop_blocks : (L + B - 1) / B, Lr = nblocks * B;
     std::vector<float *> din(Cf), dout(C);
     for (uint32_t c = 0; c < Cf; ++c) HIPCK(hipMalloc(&din[c], (L ? L : 1) * sizeof(float)));
-    for (uint32_t c = 0; c < C; ++c) HIPCK(hipMalloc(&dout[c], Lr * sizeof(float)));
     if ((st = dsp_wav_decode(d_pay, &info, 0, L, din.data(), &ex))) return fail("dsp_wav_decode", st);
+    if (conv_rate && conv_rate != info.sample_rate) {  // --rate: the file at the new rate replaces the decoded one
+        uint64_t Ln = 0;
+        if ((st = dsp_resample_plan(info.sample_rate, conv_rate, L, nullptr, nullptr, nullptr, nullptr, &Ln, nullptr)))
+            return fail("dsp_resample_plan", st);
+        std::vector<float *> dnew(Cf);
+        for (uint32_t c = 0; c < Cf; ++c) HIPCK(hipMalloc(&dnew[c], (Ln ? Ln : 1) * sizeof(float)));
+        if ((st = dsp_resample(din.data(), Cf, L, dnew.data(), Ln, info.sample_rate, conv_rate, nullptr, &ex)))
+            return fail("dsp_resample", st);
+        HIPCK(hipStreamSynchronize(s));
+        for (uint32_t c = 0; c < Cf; ++c) {
+            HIPCK(hipFree(din[c]));
+            din[c] = dnew[c];
+        }
+        L = Ln;
+    }
+    const uint64_t nblocks = loop_blocks ? loop_blocks : (L + B - 1) / B, Lr = nblocks * B;
+    for (uint32_t c = 0; c < C; ++c) HIPCK(hipMalloc(&dout[c], Lr * sizeof(float)));
 
     // ---- plugin ------------------------------------------------------------
     dsp_plugin p{};
@@ -293,9 +327,31 @@ int main(int argc, char **argv) {
         std::vector<float *> dir(ii.channels);
         for (uint32_t c = 0; c < ii.channels; ++c) HIPCK(hipMalloc(&dir[c], ii.frames * sizeof(float)));
         if ((st = dsp_wav_decode(d_ir, &ii, 0, ii.frames, dir.data(), &ex))) return fail("dsp_wav_decode", st);
-        taps.resize(ii.frames);
-        HIPCK(hipMemcpyAsync(taps.data(), dir[0], ii.frames * sizeof(float), hipMemcpyDeviceToHost, s));
+        uint64_t ntaps = ii.frames;
+        float tap_scale = 1.f;
+        if (conv_rate && conv_rate != ii.sample_rate) {  // --rate: the response at the render's rate, DC gain kept
+            if ((st = dsp_resample_plan(ii.sample_rate, conv_rate, ii.frames, nullptr, nullptr, nullptr, nullptr, &ntaps,
+                                        nullptr)))
+                return fail("dsp_resample_plan (impulse response)", st);
+            if (ntaps == 0 || ntaps > (1u << 20)) {
+                std::fprintf(stderr, "dspbench_render: %s: %llu taps at %u Hz (1..2^20 supported)\n", conv_path.c_str(),
+                             (unsigned long long)ntaps, conv_rate);
+                return 1;
+            }
+            float *dres = nullptr;
+            HIPCK(hipMalloc(&dres, ntaps * sizeof(float)));
+            if ((st = dsp_resample(dir.data(), 1, ii.frames, &dres, ntaps, ii.sample_rate, conv_rate, nullptr, &ex)))
+                return fail("dsp_resample (impulse response)", st);
+            HIPCK(hipStreamSynchronize(s));
+            HIPCK(hipFree(dir[0]));
+            dir[0] = dres;
+            tap_scale = (float)((double)ii.sample_rate / (double)conv_rate);
+        }
+        taps.resize(ntaps);
+        HIPCK(hipMemcpyAsync(taps.data(), dir[0], ntaps * sizeof(float), hipMemcpyDeviceToHost, s));
         HIPCK(hipStreamSynchronize(s));
+        if (tap_scale != 1.f)
+            for (float &t : taps) t *= tap_scale;
         for (float *q : dir) HIPCK(hipFree(q));
         HIPCK(hipFree(d_ir));
         p.kind = DSP_PLUGIN_CONV, p.params = taps.data(), p.params_size = (uint32_t)(taps.size() * sizeof(float));

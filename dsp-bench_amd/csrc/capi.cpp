@@ -100,6 +100,7 @@ struct DeviceRes {
     TableCache fir;                                            // FIR filters seen (plugin_map)
     TableCache iir;                                            // biquad cascades seen (plugin_map)
     TableCache conv;                                           // CONV impulse responses seen (plugin_map)
+    TableCache resample;                                       // dsp_resample conversions seen (up, down, spec)
     std::map<void *, IirWork> iir_work;                        // per stream
     uint32_t *iir_fb_host = nullptr, *iir_fb_dev = nullptr;  // host-mapped counter of repaired launches
     float *delta = nullptr;  // 2048 floats: 1, 0, 0, ... (compute_IR's impulse, read-only)
@@ -1264,6 +1265,110 @@ int dsp_conv_plan(uint32_t taps, uint64_t L, uint32_t B, uint32_t C, uint32_t *p
                   uint64_t *scratch_bytes) {
     if (const char *why = conv_plan(taps, L, B, C, partitions, frames, scratch_bytes)) return invalid("%s", why);
     return DSP_OK;
+}
+
+// dsp_resample_plan's checks and the library's ResamplePlan (NULL spec: the defaults)
+static int resample_plan_checked(uint32_t sr_in, uint32_t sr_out, uint64_t L, const dsp_resample_spec *spec,
+                                 ResamplePlan *plan) {
+    const dsp_resample_spec def{64u, 14.769656459379492, 0.9475937167399596};
+    if (!spec) spec = &def;
+    const char *why = nullptr;
+    const int r = resample_plan(sr_in, sr_out, L, spec->zeros, spec->beta, spec->rolloff, plan, &why);
+    if (r == 0) return DSP_OK;
+    set_last_error("%s", why);
+    return r == 1 ? DSP_ERR_INVALID : DSP_ERR_UNSUPPORTED;
+}
+
+int dsp_resample_plan(uint32_t sr_in, uint32_t sr_out, uint64_t L, const dsp_resample_spec *spec, uint32_t *up,
+                      uint32_t *down, uint32_t *taps_per_phase, uint64_t *Lout, uint64_t *table_bytes) {
+    ResamplePlan p;
+    if (int st = resample_plan_checked(sr_in, sr_out, L, spec, &p)) return st;
+    if (up) *up = p.up;
+    if (down) *down = p.down;
+    if (taps_per_phase) *taps_per_phase = p.taps;
+    if (Lout) *Lout = p.Lout;
+    if (table_bytes) *table_bytes = p.table_bytes;
+    return DSP_OK;
+}
+
+int dsp_resample_taps(uint32_t sr_in, uint32_t sr_out, const dsp_resample_spec *spec, float *table, uint64_t count) {
+    ResamplePlan p;
+    if (int st = resample_plan_checked(sr_in, sr_out, 0, spec, &p)) return st;
+    if (!table) return invalid("dsp_resample_taps: NULL table");
+    if (count != (uint64_t)p.up * p.taps)
+        return invalid("dsp_resample_taps: count %llu != up * taps = %llu", (unsigned long long)count,
+                       (unsigned long long)p.up * p.taps);
+    resample_table(p, table, p.taps, 0);
+    return DSP_OK;
+}
+
+int dsp_resample(const float *const *in, uint32_t C, uint64_t L, float *const *out, uint64_t Lout, uint32_t sr_in,
+                 uint32_t sr_out, const dsp_resample_spec *spec, const dsp_exec *ex) {
+    ResamplePlan p;
+    int st;
+    if ((st = resample_plan_checked(sr_in, sr_out, L, spec, &p))) return st;
+    if (Lout != p.Lout)
+        return invalid("dsp_resample: Lout %llu != the plan's %llu", (unsigned long long)Lout,
+                       (unsigned long long)p.Lout);
+    if (goff_of(ex) != 0) return invalid("dsp_resample: whole rows only (sample_offset 0)");
+    if (C == 0 || L == 0) return DSP_OK;
+    if ((st = check_rows("out", out, C)) || (st = check_rows("in", in, C))) return st;
+    if (rows_overlap(in, C, L, out, C, Lout)) return invalid("dsp_resample: output rows overlap input rows");
+    DeviceGuard g(ex);
+    if (g.status) return g.status;
+    hipStream_t s = stream_of(ex);
+    Stage stage(ex);
+    const std::vector<const float *> din = stage.in_rows(in, C, L);
+    const std::vector<float *> dout = stage.out_rows(out, C, Lout);
+    if (stage.status) return stage.status;
+    if (p.up == 1 && p.down == 1) {  // the same rate: a copy, no filter
+        for (uint32_t c = 0; c < C; ++c)
+            DSPB_HIP(hipMemcpyAsync(dout[c], din[c], L * sizeof(float), hipMemcpyDeviceToDevice, s));
+        return (st = stage.copy_back()) ? st : finish(ex);
+    }
+    ResampleArgs A{};
+    A.L = L;
+    A.Lout = Lout;
+    A.up = p.up;
+    A.down = p.down;
+    A.half = p.half;
+    A.Tp = p.taps;
+    resample_blocking(&A);
+    DevTable table;  // held until the call's launches are enqueued
+    {
+        // (a double as three floats: the key compares by value)
+        auto split = [](double v, std::vector<float> &k) {
+            const float a = (float)v, b = (float)(v - (double)a), c = (float)(v - (double)a - (double)b);
+            k.insert(k.end(), {a, b, c});
+        };
+        std::vector<float> key{(float)p.up, (float)p.down, (float)p.zeros};
+        split(p.beta, key);
+        split(p.rolloff, key);
+        std::lock_guard<std::mutex> lk(g_mu);
+        const CachedTable *rt = nullptr;
+        st = cached_table(g_res[g.dev].resample, key, g.dev, s, "a sample-rate conversion's filter table",
+                          [&](std::vector<float> &h, CachedTable &) {
+            std::vector<float> plain((size_t)p.up * p.taps);
+            resample_table(p, plain.data(), p.taps, 0);
+            h.resize(resample_device_floats(A));
+            resample_device_table(A, plain.data(), h.data());
+        }, &rt, kConvCacheBytes);
+        if (st) return st;
+        table = rt->dev;
+    }
+    A.table = table.get();
+    st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
+        ResampleArgs G = A;
+        G.out_aligned16 = 1;
+        for (uint32_t j = 0; j < cn; ++j) {
+            G.in.p[j] = din[c0 + j];
+            G.out.p[j] = dout[c0 + j];
+            if (!aligned(dout[c0 + j], 16)) G.out_aligned16 = 0;
+        }
+        return launch_resample(G, cn, s);
+    });
+    if (st) return st;
+    return (st = stage.copy_back()) ? st : finish(ex);
 }
 
 uint64_t dsp_stft_frame_count(uint64_t L, uint32_t N, uint32_t H) {

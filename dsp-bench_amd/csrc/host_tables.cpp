@@ -115,6 +115,68 @@ const char *conv_plan(uint32_t taps, uint64_t L, uint32_t B, uint32_t C, uint32_
     return nullptr;
 }
 
+static double bessel_i0(double x);
+
+// dsp_resample: the plan of a rate pair and quality, all in integers and float64
+int resample_plan(uint32_t sr_in, uint32_t sr_out, uint64_t L, uint32_t zeros, double beta, double rolloff,
+                  ResamplePlan *plan, const char **why) {
+    const char *dummy;
+    if (!why) why = &dummy;
+    if (sr_in == 0 || sr_out == 0) return *why = "dsp_resample: sample rates must be >= 1", 1;
+    if (zeros < 4 || zeros > 64) return *why = "dsp_resample: zeros must be 4..64", 1;
+    if (!(beta >= 0.0 && beta <= 20.0)) return *why = "dsp_resample: beta must be 0..20", 1;
+    if (!(rolloff >= 0.5 && rolloff <= 1.0)) return *why = "dsp_resample: rolloff must be 0.5..1", 1;
+    uint32_t a = sr_in, b = sr_out;
+    while (b) { const uint32_t t = a % b; a = b; b = t; }
+    ResamplePlan p;
+    p.up = sr_out / a;
+    p.down = sr_in / a;
+    p.zeros = zeros;
+    p.beta = beta;
+    p.rolloff = rolloff;
+    p.rho = rolloff * std::min(1.0, (double)p.up / (double)p.down);
+    p.W = (double)zeros / p.rho;
+    if (p.up > kResampleMaxUp) return *why = "dsp_resample: sr_out / gcd > 4096", 2;
+    if (std::ceil(p.W) * 2.0 > (double)kResampleMaxTaps) return *why = "dsp_resample: more than 8192 taps per phase", 2;
+    p.half = (uint32_t)std::ceil(p.W);
+    p.taps = 2 * p.half;
+    p.table_bytes = (uint64_t)p.up * p.taps * sizeof(float);
+    if (p.table_bytes > kResampleMaxTableBytes) return *why = "dsp_resample: table larger than 8 MiB", 2;
+    if (L > ((1ull << 63) - p.down) / p.up) return *why = "dsp_resample: L up overflows 2^63", 2;
+    p.Lout = (L * p.up + p.down - 1) / p.down;
+    p.inv_i0_beta = 1.0 / bessel_i0(beta);
+    if (plan) *plan = p;
+    return 0;
+}
+
+// I0 by its power series sum ((x / 2)^k / k!)^2, to convergence in float64
+static double bessel_i0(double x) {
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 1000; ++k) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+        if (term < 1e-17 * sum) break;
+    }
+    return sum;
+}
+
+double resample_h(const ResamplePlan &p, double u) {
+    if (!(std::fabs(u) < p.W)) return 0.0;
+    const double t = p.rho * u, r = u / p.W;
+    const double sinc = t == 0.0 ? 1.0 : std::sin(M_PI * t) / (M_PI * t);
+    return p.rho * sinc * bessel_i0(p.beta * std::sqrt(std::max(0.0, 1.0 - r * r))) * p.inv_i0_beta;
+}
+
+void resample_table(const ResamplePlan &p, float *out, uint64_t row_stride, uint64_t row_offset) {
+    for (uint32_t phi = 0; phi < p.up; ++phi) {
+        float *row = out + phi * row_stride + row_offset;
+        const double frac = (double)phi / (double)p.up;
+        for (uint32_t i = 0; i < p.taps; ++i)
+            row[i] = (float)resample_h(p, ((double)p.half - 1.0 - (double)i) + frac);
+    }
+}
+
 // IR_test (build/IR_test.cpp:47-58) runs `gain -= step` in double from the
 // float parameters.  The sequence is often exact -- every partial result a
 // double -- and then table[i] = (float)(gain - i step) is one f64 FMA, with

@@ -31,6 +31,27 @@ void conv_table(const float *taps, uint32_t T, float *out);
 // Any out pointer may be null.  Returns null, or why the arguments are invalid.
 const char *conv_plan(uint32_t taps, uint64_t L, uint32_t B, uint32_t C, uint32_t *partitions, uint64_t *frames,
                       uint64_t *scratch_bytes);
+// dsp_resample (resample.hip): the polyphase Kaiser-windowed sinc of
+// dspbench.h.  up = sr_out / g, down = sr_in / g; rho = rolloff min(1, up /
+// down), W = zeros / rho, half = ceil(W), taps = 2 half per phase
+struct ResamplePlan {
+    uint32_t up = 0, down = 0, half = 0, taps = 0;
+    uint32_t zeros = 0;
+    double beta = 0.0, rolloff = 0.0, rho = 0.0, W = 0.0;
+    double inv_i0_beta = 1.0;  // 1 / I0(beta)
+    uint64_t Lout = 0;         // ceil(L up / down)
+    uint64_t table_bytes = 0;  // up taps floats
+};
+constexpr uint32_t kResampleMaxUp = 4096, kResampleMaxTaps = 8192;
+constexpr uint64_t kResampleMaxTableBytes = 8ull << 20;
+// dsp_resample_plan's body.  Returns 0, or 1 (invalid) / 2 (unsupported) with *why set.
+int resample_plan(uint32_t sr_in, uint32_t sr_out, uint64_t L, uint32_t zeros, double beta, double rolloff,
+                  ResamplePlan *plan, const char **why);
+// h(u) of the plan in float64 (zero for |u| >= W)
+double resample_h(const ResamplePlan &p, double u);
+// table[phi][i] = (float)h(half - 1 - i + phi / up), phi < up, i < taps; row
+// phi at out + phi * row_stride + row_offset (the other floats are left alone)
+void resample_table(const ResamplePlan &p, float *out, uint64_t row_stride, uint64_t row_offset);
 // whether IR_test's `gain -= step` recurrence equals (float)fma(-i, step, gain) for every i < B
 bool ramp_closed_form(float gain, float step, uint32_t B);
 // a cascade's tables for lanes of `lane_samples` samples (iir.hip biquad_lane_samples()); returns W

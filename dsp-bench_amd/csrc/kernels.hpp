@@ -137,6 +137,28 @@ struct ConvArgs {
     const v2f *tw;       // T8192 + lane-major stage twiddles (capi.cpp get_tw)
 };
 int launch_conv(const ConvArgs &A, uint32_t C, hipStream_t s);
+// dsp_resample (resample.hip): one launch converts C <= 16 channels.  up,
+// down, half, Tp are the plan's (host_tables.hpp ResamplePlan);
+// resample_blocking derives the rest from them, and `table` holds
+// resample_device_table's layout for that blocking
+struct ResampleArgs {
+    ChanIn in;
+    ChanOut out;
+    uint64_t L, Lout;
+    const float *table;
+    uint32_t up, down, half, Tp;
+    uint32_t phase;          // 1: resample_phase_kernel<R>; 0: resample_direct_kernel
+    uint32_t R, S;           // phases per group; steps of a group's sweep (a multiple of 4)
+    uint32_t JC;             // 64-period chunks per tile
+    uint32_t a, hreg;        // down = odd << a; floats per LDS region of the staged input
+    uint32_t xspan, xfloats; // staged inputs per tile; floats of LDS they take
+    uint32_t lds_bytes;
+    uint32_t out_aligned16;  // every output row is 16-byte aligned
+};
+void resample_blocking(ResampleArgs *A);
+uint64_t resample_device_floats(const ResampleArgs &A);
+void resample_device_table(const ResampleArgs &A, const float *plain, float *out);
+int launch_resample(const ResampleArgs &A, uint32_t C, hipStream_t s);
 // DSP_PLUGIN_BIQUAD (iir.hip): one launch renders C <= 16 channels of Ly
 // samples from zero state; tiles of 64 lanes x biquad_lane_samples() samples
 struct BiquadArgs {

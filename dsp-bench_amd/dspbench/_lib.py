@@ -63,6 +63,10 @@ class dsp_exec(C.Structure):
                 ("sample_offset", C.c_uint64), ("result", C.POINTER(C.c_uint32))]
 
 
+class dsp_resample_spec(C.Structure):
+    _fields_ = [("zeros", C.c_uint32), ("beta", C.c_double), ("rolloff", C.c_double)]
+
+
 DSP_WAV_FORMAT_PCM = 1
 DSP_WAV_FORMAT_FLOAT = 3
 DSP_WAV_MAX_DATA_CHUNKS = 8
@@ -144,6 +148,12 @@ _SIGS = {
     "dsp_stft_frame_count": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32]),
     "dsp_conv_plan": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dsp_resample_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(dsp_resample_spec),
+                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dsp_resample_taps": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(dsp_resample_spec), FP, C.c_uint64]),
+    "dsp_resample": (C.c_int, [FPP, C.c_uint32, C.c_uint64, FPP, C.c_uint64, C.c_uint32, C.c_uint32,
+                               C.POINTER(dsp_resample_spec), C.POINTER(dsp_exec)]),
     "dsp_render_offline": (C.c_int, [FPP, C.c_uint32, C.c_uint64, FPP, C.c_uint32, C.c_uint32,
                                      C.c_float, C.POINTER(dsp_plugin), C.POINTER(dsp_exec)]),
     "dsp_render_loop": (C.c_int, [FPP, C.c_uint32, C.c_uint64, C.c_uint64, FPP, C.c_uint32, C.c_uint32,

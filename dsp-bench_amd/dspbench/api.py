@@ -157,6 +157,51 @@ def conv_plan(taps: int, L_: int, B: int, C_out: int) -> tuple[int, int, int]:
     return p.value, f.value, b.value
 
 
+def _resample_spec(zeros, beta, rolloff):
+    """The three quality fields as a dsp_resample_spec, or None (the library's
+    defaults) when none is given; a field left out takes its default."""
+    if zeros is None and beta is None and rolloff is None:
+        return None
+    return L.dsp_resample_spec(64 if zeros is None else zeros, 14.769656459379492 if beta is None else beta,
+                               0.9475937167399596 if rolloff is None else rolloff)
+
+
+def resample_plan(sr_in: int, sr_out: int, L_: int = 0, zeros=None, beta=None, rolloff=None) -> dict:
+    """dsp_resample_plan (host only): up, down, taps per phase, Lout and the
+    table's bytes of a conversion of L_ samples."""
+    spec = _resample_spec(zeros, beta, rolloff)
+    up, down, taps, lout, tb = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+    check(L.lib().dsp_resample_plan(sr_in, sr_out, L_, C.byref(spec) if spec is not None else None, C.byref(up),
+                                    C.byref(down), C.byref(taps), C.byref(lout), C.byref(tb)), "dsp_resample_plan")
+    return {"up": up.value, "down": down.value, "taps": taps.value, "Lout": lout.value, "table_bytes": tb.value}
+
+
+def resample_taps(sr_in: int, sr_out: int, zeros=None, beta=None, rolloff=None):
+    """dsp_resample_taps (host only): the conversion's table [up, taps] float32."""
+    p = resample_plan(sr_in, sr_out, 0, zeros, beta, rolloff)
+    spec = _resample_spec(zeros, beta, rolloff)
+    t = np.empty((p["up"], p["taps"]), np.float32)
+    check(L.lib().dsp_resample_taps(sr_in, sr_out, C.byref(spec) if spec is not None else None, _fp(t), t.size),
+          "dsp_resample_taps")
+    return t
+
+
+def resample(x, sr_in: int, sr_out: int, zeros=None, beta=None, rolloff=None, stream=None, out=None):
+    """Sample-rate conversion of x [C, L] (torch CUDA tensor, or numpy on the
+    host) from sr_in to sr_out (dsp_resample).  Returns [C, Lout]."""
+    in_ptrs, ref = _rows(x)
+    L_ = int(x.shape[1])
+    lout = resample_plan(sr_in, sr_out, L_, zeros, beta, rolloff)["Lout"]
+    if out is None:
+        out = _alloc_like(ref, (len(in_ptrs), max(lout, 1)))
+    out_ptrs, _ = _rows(out)
+    spec = _resample_spec(zeros, beta, rolloff)
+    ex = _exec(ref, 0, stream)
+    check(L.lib().dsp_resample(chan_table(in_ptrs), len(in_ptrs), L_, chan_table(out_ptrs), lout, sr_in, sr_out,
+                               C.byref(spec) if spec is not None else None, C.byref(ex)), "dsp_resample")
+    return out[:, :lout]
+
+
 def stft_frames(L_: int, N: int, H: int) -> int:
     return int(L.lib().dsp_stft_frame_count(L_, N, H))
 

@@ -181,6 +181,59 @@ int dsp_biquad_plan(const float *coef, uint32_t sections, uint32_t *window);
 int dsp_conv_plan(uint32_t taps, uint64_t L, uint32_t B, uint32_t C,
                   uint32_t *partitions, uint64_t *frames, uint64_t *scratch_bytes);
 
+/* Sample-rate conversion: a polyphase Kaiser-windowed sinc, zero-phase.
+ *
+ * With g = gcd(sr_in, sr_out): up = sr_out / g, down = sr_in / g.  A quality
+ * spec is zeros Z (zero crossings each side, 4..64), the Kaiser beta (0..20)
+ * and rolloff (0.5..1); a NULL spec is Z = 64, beta = 14.769656459379492,
+ * rolloff = 0.9475937167399596 ("kaiser best").
+ *   rho = rolloff min(1, up / down), W = Z / rho, half = ceil(W),
+ *   taps per phase Tp = 2 half,
+ *   h(u) = rho sinc(rho u) I0(beta sqrt(1 - (u / W)^2)) / I0(beta) for |u| < W,
+ *          0 otherwise (sinc(t) = sin(pi t) / (pi t)),
+ *   table[phi][i] = (float)h(half - 1 - i + phi / up), phi < up, i < Tp
+ *                   (float64, rounded once),
+ *   Lout = ceil(L up / down),
+ *   y[m] = sum_{i < Tp} table[phi][i] x[n0 - half + 1 + i], q = m down (64-bit),
+ *          n0 = q / up, phi = q % up, x = 0 outside [0, L).
+ * Output m sits at input time m down / up: no delay to compensate.  The sum's
+ * order is the kernel's own (fp32, within a bound of float64; taps outside an
+ * output's window enter as zero products, so samples must be finite).
+ * sr_in == sr_out is a copy, bit for bit, with no filter.
+ *
+ * Refused with DSP_ERR_UNSUPPORTED: up > 4096, Tp > 8192, a table (up Tp
+ * floats) above 8 MiB, L up >= 2^63.  Every pair of the standard rates 8000,
+ * 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000,
+ * 176400, 192000 plans at the default quality: none is refused (the largest
+ * are 192000 -> 8000, Tp = 3242, and 192000 -> 11025, a 1.4 MB table;
+ * tests/test_resample_plan.py checks the list against dsp_resample_plan). */
+typedef struct dsp_resample_spec {
+    uint32_t zeros;  /* 4..64 */
+    double beta;     /* 0..20 */
+    double rolloff;  /* 0.5..1 */
+} dsp_resample_spec;
+
+/* The plan of a conversion (host only, no device).  Any out pointer may be
+ * NULL.  DSP_ERR_INVALID for a rate of 0 or a spec outside its ranges;
+ * DSP_ERR_UNSUPPORTED as above. */
+int dsp_resample_plan(uint32_t sr_in, uint32_t sr_out, uint64_t L, const dsp_resample_spec *spec,
+                      uint32_t *up, uint32_t *down, uint32_t *taps_per_phase, uint64_t *Lout,
+                      uint64_t *table_bytes);
+
+/* The conversion's table[phi][i], up rows of Tp floats, as the device uses it
+ * (host only).  count must be up Tp (DSP_ERR_INVALID otherwise). */
+int dsp_resample_taps(uint32_t sr_in, uint32_t sr_out, const dsp_resample_spec *spec, float *table,
+                      uint64_t count);
+
+/* Converts C rows of L samples at sr_in into rows of Lout samples at sr_out
+ * (Lout must equal the plan's).  Device rows, or host rows with
+ * DSP_EXEC_HOST_BUFFERS.  Output rows must not overlap input rows and
+ * ex->sample_offset must be 0 (DSP_ERR_INVALID).  L = 0 is DSP_OK and writes
+ * nothing.  The device table is cached per device by (up, down, spec); a
+ * stream being captured needs one eager call of the conversion first. */
+int dsp_resample(const float *const *in, uint32_t C, uint64_t L, float *const *out, uint64_t Lout,
+                 uint32_t sr_in, uint32_t sr_out, const dsp_resample_spec *spec, const dsp_exec *ex);
+
 /* Test hooks (not for production use).
  * DSP_DEBUG_BIQUAD_SPIN_LIMIT (set): the sleeps a DSP_PLUGIN_BIQUAD look-back
  *   waits for a preceding tile's words before it gives up (value ~0 restores
