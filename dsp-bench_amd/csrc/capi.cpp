@@ -20,6 +20,7 @@
 #include <tuple>
 #include <vector>
 
+#include "host_hip.hpp"
 #include "host_tables.hpp"
 #include "kernels.hpp"
 #include "dspbench/wav.h"
@@ -116,33 +117,12 @@ static int current_device(int *dev) {
     return DSP_OK;
 }
 
-// RAII: make ex->device current for the call, restore afterwards.
-struct DeviceGuard {
-    int prev = -1;
-    int dev = -1;
-    int status = DSP_OK;
-    explicit DeviceGuard(const dsp_exec *ex) {
-        hipError_t e = hipGetDevice(&prev);
-        if (e != hipSuccess) { status = hip_fail(e, "hipGetDevice"); return; }
-        dev = prev;
-        if (ex && ex->device >= 0 && ex->device != prev) {
-            e = hipSetDevice(ex->device);
-            if (e != hipSuccess) { status = hip_fail(e, "hipSetDevice"); return; }
-            dev = ex->device;
-        }
-    }
-    ~DeviceGuard() {
-        if (prev >= 0 && dev != prev) (void)hipSetDevice(prev);
-    }
-};
-
 // A call on a stream that is being captured into a graph cannot make a
 // first-use table or scratch allocation (an allocation, a legacy-stream
 // launch and a sync would invalidate the capture): it is refused instead, and
 // one eager call of the same shape beforehand creates what it needs.
 static int refuse_capture(hipStream_t s, const char *what) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+    if (capturing(s)) {
         set_last_error("stream capture: %s is created on first use; make one eager call of this shape on the "
                        "capturing stream first", what);
         return DSP_ERR_INVALID;
@@ -400,12 +380,9 @@ static std::atomic<uint32_t> g_iir_spin_limit{kIirSpinLimit};
 // under one lock: launches on a stream are enqueued in epoch order
 static int iir_launch(int dev, hipStream_t s, BiquadArgs *A, uint32_t sections, uint32_t nch) {
     const uint64_t tiles = (uint64_t)(A->C / nch) * A->ntiles_ch;
-    {   // every launch takes a fresh epoch: a graph replay would reuse it
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
-            set_last_error("stream capture: a BIQUAD render cannot be captured (its look-back state is per launch)");
-            return DSP_ERR_INVALID;
-        }
+    if (capturing(s)) {  // every launch takes a fresh epoch: a graph replay would reuse it
+        set_last_error("stream capture: a BIQUAD render cannot be captured (its look-back state is per launch)");
+        return DSP_ERR_INVALID;
     }
     std::lock_guard<std::mutex> lk(g_mu);
     DeviceRes &r = g_res[dev];
@@ -650,17 +627,6 @@ static int plugin_map(const dsp_plugin *p, uint32_t B, int dev, hipStream_t s, S
     default:
         return invalid("unknown plugin kind %d", p->kind);
     }
-}
-
-// whether any input row [in[c], in[c] + L) overlaps any output row [out[c'], out[c'] + Lr)
-static bool rows_overlap(const float *const *in, uint32_t in_ch, uint64_t L, const float *const *out, uint32_t C,
-                         uint64_t Lr) {
-    for (uint32_t a = 0; a < in_ch; ++a)
-        for (uint32_t b = 0; b < C; ++b) {
-            const uintptr_t i0 = reinterpret_cast<uintptr_t>(in[a]), o0 = reinterpret_cast<uintptr_t>(out[b]);
-            if (L && Lr && i0 < o0 + 4 * Lr && o0 < i0 + 4 * L) return true;
-        }
-    return false;
 }
 
 // A GENERIC plugin with a known block class (module.h dsp_module_block_class)

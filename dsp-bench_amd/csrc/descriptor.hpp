@@ -67,3 +67,9 @@ bool code_symbol(const void *code, size_t size, const char *name, std::string *o
 
 }  // namespace desc
 }  // namespace dspb
+
+// module.h's opaque descriptor (the dsp_descriptor_* / dsp_params_* /
+// dsp_param_* C API at the end of descriptor.cpp)
+struct dsp_descriptor {
+    dspb::desc::Descriptor d;
+};
