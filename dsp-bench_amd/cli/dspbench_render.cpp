@@ -42,6 +42,16 @@
 //                       ir_rate / R (the filter's DC gain is kept); it must still
 //                       be <= 2^20 taps.  Not with --device-rate, --loop or
 //                       --comm-id
+//     --loudness        measure the render (its written frames, every output
+//                       channel at weight 1: dsp_loudness with the true peak)
+//                       and print one JSON line with the result to stdout
+//     --normalize LUFS  measure, then scale the render by g = (float)10^((LUFS -
+//                       integrated) / 20) before the encode; a render that
+//                       measures -inf is an error
+//     --true-peak-ceiling DBTP   with --normalize: lower g so that true_peak g
+//                       <= 10^(DBTP / 20).  None of the three with --loop or the
+//                       multi-GPU modes.  --stft's magnitudes are those of the
+//                       render before this gain (the fused render + STFT)
 //     --loop NBLOCKS    loop mode (audio.cpp:100-132): NBLOCKS blocks from a
 //                       file that wraps around (no --stft)
 //   multi-GPU (cfg 5, shard.h): one process per GPU, channels sharded one
@@ -64,6 +74,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -109,6 +120,7 @@ void usage() {
                  "       [--convolve IR.wav] [--gain G] [--ir G,STEP] [--block B] [--bits 16|24|32|float] [--stft MAG.f32]"
                  " [--device N]\n"
                  "       [--device-channels C] [--device-rate R] [--rate R] [--loop NBLOCKS]\n"
+                 "       [--loudness] [--normalize LUFS [--true-peak-ceiling DBTP]]\n"
                  "       [--world W --rank R --comm-id FILE [--run-id STR] [--chunk SAMPLES]]\n");
 }
 
@@ -147,6 +159,15 @@ bool exchange_comm_id(const std::string &path, uint32_t rank, const std::string 
     return false;
 }
 
+// a double as a JSON number (Python's json reads the three non-finite tokens)
+std::string json_num(double v) {
+    if (std::isnan(v)) return "NaN";
+    if (std::isinf(v)) return v < 0 ? "-Infinity" : "Infinity";
+    char b[40];
+    std::snprintf(b, sizeof b, "%.17g", v);
+    return b;
+}
+
 double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -167,12 +188,19 @@ int main(int argc, char **argv) {
     uint32_t dev_channels = 0, dev_rate = 0, conv_rate = 0, world = 0, rank = 0;
     uint64_t loop_blocks = 0, chunk = 16ull << 20;
     bool have_rank = false;
+    bool want_loudness = false, want_normalize = false, want_ceiling = false;
+    double norm_lufs = 0.0, ceiling_dbtp = 0.0;
     std::string comm_path, run_id;
     const time_t started = std::time(nullptr) - 2;  // (mtime has one-second resolution)
     if (const char *e = std::getenv("DSPB_RUN_ID")) run_id = e;
     else if (const char *e2 = std::getenv("TORCHELASTIC_RUN_ID")) run_id = e2;
-    for (int i = 3; i < argc; i += 2) {  // every option takes one value
+    for (int i = 3; i < argc; i += 2) {  // every option but --loudness takes one value
         const std::string a = argv[i];
+        if (a == "--loudness") {
+            want_loudness = true;
+            --i;
+            continue;
+        }
         const char *v = i + 1 < argc ? argv[i + 1] : nullptr;
         if (!v) {
             usage();
@@ -198,7 +226,17 @@ int main(int argc, char **argv) {
                 usage();
                 return 2;
             }
-        } else if (a == "--loop") loop_blocks = std::strtoull(v, nullptr, 10);
+        } else if (a == "--normalize" || a == "--true-peak-ceiling") {
+            char *end = nullptr;
+            const double val = std::strtod(v, &end);
+            if (end == v || *end) {  // not a number
+                usage();
+                return 2;
+            }
+            if (a == "--normalize") norm_lufs = val, want_normalize = true;
+            else ceiling_dbtp = val, want_ceiling = true;
+        }
+        else if (a == "--loop") loop_blocks = std::strtoull(v, nullptr, 10);
         else if (a == "--world") world = (uint32_t)std::strtoul(v, nullptr, 10);
         else if (a == "--rank") rank = (uint32_t)std::strtoul(v, nullptr, 10), have_rank = true;
         else if (a == "--comm-id") comm_path = v;
@@ -220,6 +258,21 @@ int main(int argc, char **argv) {
     const bool multi = !comm_path.empty();
     if (conv_rate && (dev_rate || loop_blocks || multi || world)) {
         std::fprintf(stderr, "dspbench_render: --rate excludes --device-rate, --loop and the multi-GPU modes\n");
+        usage();
+        return 2;
+    }
+    if ((want_loudness || want_normalize || want_ceiling) && (loop_blocks || multi || world)) {
+        std::fprintf(stderr, "dspbench_render: --loudness, --normalize and --true-peak-ceiling exclude --loop and the "
+                             "multi-GPU modes\n");
+        usage();
+        return 2;
+    }
+    if (want_ceiling && !want_normalize) {
+        std::fprintf(stderr, "dspbench_render: --true-peak-ceiling needs --normalize\n");
+        usage();
+        return 2;
+    }
+    if ((want_normalize && !std::isfinite(norm_lufs)) || (want_ceiling && !std::isfinite(ceiling_dbtp))) {
         usage();
         return 2;
     }
@@ -465,6 +518,41 @@ int main(int argc, char **argv) {
                     world, ms);
         dsp_comm_destroy(comm);
         return 0;
+    }
+
+    // ---- loudness of the render, and the gain to a target level ------------
+    if (want_loudness || want_normalize) {
+        dsp_loudness_result lr{};
+        if ((st = dsp_loudness(dout.data(), C, Lr, rate, nullptr, DSP_LOUDNESS_TRUE_PEAK, nullptr, nullptr, nullptr, &lr,
+                               &ex)))
+            return fail("dsp_loudness", st);
+        float g = 1.f;
+        if (want_normalize) {
+            if (!std::isfinite(lr.integrated)) {
+                std::fprintf(stderr, "dspbench_render: --normalize: the render's integrated loudness is %s "
+                                     "(no block passes the gates)\n", json_num(lr.integrated).c_str());
+                return 1;
+            }
+            g = (float)std::pow(10.0, (norm_lufs - lr.integrated) / 20.0);
+            if (want_ceiling) {
+                const double limit = std::pow(10.0, ceiling_dbtp / 20.0);
+                if (lr.true_peak * (double)g > limit) {
+                    g = (float)(limit / lr.true_peak);
+                    while (g > 0.f && lr.true_peak * (double)g > limit) g = std::nextafterf(g, 0.f);
+                }
+            }
+            for (uint32_t c = 0; c < C; ++c)
+                if ((st = dsp_gain(dout[c], dout[c], g, Lr, &ex))) return fail("dsp_gain", st);
+        }
+        if (want_loudness) {
+            std::string j = "{\"integrated\": " + json_num(lr.integrated) + ", \"range\": " + json_num(lr.range) +
+                            ", \"momentary_max\": " + json_num(lr.momentary_max) + ", \"short_term_max\": " +
+                            json_num(lr.short_term_max) + ", \"sample_peak\": " + json_num(lr.sample_peak) +
+                            ", \"true_peak\": " + json_num(lr.true_peak) + ", \"blocks\": " +
+                            std::to_string(lr.blocks) + ", \"gated_blocks\": " + std::to_string(lr.gated_blocks);
+            if (want_normalize) j += ", \"gain\": " + json_num((double)g);
+            std::printf("%s}\n", j.c_str());
+        }
     }
 
     // ---- encode the render (audio.h:123-133 interleave) and write ----------

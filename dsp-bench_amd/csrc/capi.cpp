@@ -23,6 +23,7 @@
 #include "host_hip.hpp"
 #include "host_tables.hpp"
 #include "kernels.hpp"
+#include "loudness_host.hpp"
 #include "dspbench/wav.h"
 
 namespace dspb {
@@ -266,7 +267,8 @@ static int set_wincomp(int dev, hipStream_t s, int kind, Stft8kArgs *A) {
 
 // Stream-ordered scratch: calls on one stream are serialised by the stream,
 // so one buffer per (device, stream, slot) is enough.  Slots: 0 the IR_test
-// block table, 1 loop mode's wrapped file, 2 a CONV channel group's spectra.
+// block table, 1 loop mode's wrapped file, 2 a CONV channel group's spectra,
+// 3 a dsp_loudness channel group's partial sums, hop energies and peaks.
 static int get_scratch(int dev, hipStream_t s, size_t bytes, float **out, int slot_id = 0) {
     std::lock_guard<std::mutex> lk(g_mu);
     DeviceRes &r = g_res[dev];
@@ -1268,6 +1270,32 @@ int dsp_resample_taps(uint32_t sr_in, uint32_t sr_out, const dsp_resample_spec *
     return DSP_OK;
 }
 
+// The device table of a conversion's blocking (resample.hip), cached per device
+// by (up, down, spec); *table is the caller's hold on it.
+static int resample_cached_table(const ResamplePlan &p, const ResampleArgs &A, int dev, hipStream_t s,
+                                 DevTable *table) {
+    // (a double as three floats: the key compares by value)
+    auto split = [](double v, std::vector<float> &k) {
+        const float a = (float)v, b = (float)(v - (double)a), c = (float)(v - (double)a - (double)b);
+        k.insert(k.end(), {a, b, c});
+    };
+    std::vector<float> key{(float)p.up, (float)p.down, (float)p.zeros};
+    split(p.beta, key);
+    split(p.rolloff, key);
+    std::lock_guard<std::mutex> lk(g_mu);
+    const CachedTable *rt = nullptr;
+    const int st = cached_table(g_res[dev].resample, key, dev, s, "a sample-rate conversion's filter table",
+                                [&](std::vector<float> &h, CachedTable &) {
+        std::vector<float> plain((size_t)p.up * p.taps);
+        resample_table(p, plain.data(), p.taps, 0);
+        h.resize(resample_device_floats(A));
+        resample_device_table(A, plain.data(), h.data());
+    }, &rt, kConvCacheBytes);
+    if (st) return st;
+    *table = rt->dev;
+    return DSP_OK;
+}
+
 int dsp_resample(const float *const *in, uint32_t C, uint64_t L, float *const *out, uint64_t Lout, uint32_t sr_in,
                  uint32_t sr_out, const dsp_resample_spec *spec, const dsp_exec *ex) {
     ResamplePlan p;
@@ -1301,27 +1329,7 @@ int dsp_resample(const float *const *in, uint32_t C, uint64_t L, float *const *o
     A.Tp = p.taps;
     resample_blocking(&A);
     DevTable table;  // held until the call's launches are enqueued
-    {
-        // (a double as three floats: the key compares by value)
-        auto split = [](double v, std::vector<float> &k) {
-            const float a = (float)v, b = (float)(v - (double)a), c = (float)(v - (double)a - (double)b);
-            k.insert(k.end(), {a, b, c});
-        };
-        std::vector<float> key{(float)p.up, (float)p.down, (float)p.zeros};
-        split(p.beta, key);
-        split(p.rolloff, key);
-        std::lock_guard<std::mutex> lk(g_mu);
-        const CachedTable *rt = nullptr;
-        st = cached_table(g_res[g.dev].resample, key, g.dev, s, "a sample-rate conversion's filter table",
-                          [&](std::vector<float> &h, CachedTable &) {
-            std::vector<float> plain((size_t)p.up * p.taps);
-            resample_table(p, plain.data(), p.taps, 0);
-            h.resize(resample_device_floats(A));
-            resample_device_table(A, plain.data(), h.data());
-        }, &rt, kConvCacheBytes);
-        if (st) return st;
-        table = rt->dev;
-    }
+    if ((st = resample_cached_table(p, A, g.dev, s, &table))) return st;
     A.table = table.get();
     st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
         ResampleArgs G = A;
@@ -1335,6 +1343,161 @@ int dsp_resample(const float *const *in, uint32_t C, uint64_t L, float *const *o
     });
     if (st) return st;
     return (st = stage.copy_back()) ? st : finish(ex);
+}
+
+static int loudness_plan_checked(uint32_t sr, uint64_t L, LoudnessPlan *p) {
+    const char *why = nullptr;
+    if (loudness_plan(sr, L, p, &why) == 0) return DSP_OK;
+    set_last_error("%s", why);
+    return DSP_ERR_UNSUPPORTED;
+}
+
+int dsp_loudness_plan(uint32_t sr, uint64_t L, uint32_t *hop, uint64_t *hops, uint32_t *oversample, float kcoef[10],
+                      uint64_t *scratch_bytes) {
+    LoudnessPlan p;
+    if (int st = loudness_plan_checked(sr, L, &p)) return st;
+    if (hop) *hop = p.hop;
+    if (hops) *hops = p.hops;
+    if (oversample) *oversample = p.oversample;
+    if (kcoef) std::memcpy(kcoef, p.kcoef, sizeof p.kcoef);
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    return DSP_OK;
+}
+
+int dsp_loudness_gate(const double *const *hop_energy, uint32_t C, uint64_t hops, uint32_t hop, const float *weights,
+                      dsp_loudness_result *res) {
+    if (!res || C == 0 || hop == 0) return invalid("dsp_loudness_gate: needs res, C >= 1 and hop >= 1");
+    if (hops) {
+        if (!hop_energy) return invalid("hop_energy is NULL");
+        for (uint32_t c = 0; c < C; ++c)
+            if (!hop_energy[c]) return invalid("hop_energy[%u] is NULL", c);
+    }
+    loudness_gate(hop_energy, C, hops, hop, weights, res);
+    return DSP_OK;
+}
+
+int dsp_loudness(const float *const *in, uint32_t C, uint64_t L, uint32_t sr, const float *weights, uint32_t flags,
+                 const dsp_resample_spec *tp_spec, double *const *hop_energy, double *chan_peaks,
+                 dsp_loudness_result *res, const dsp_exec *ex) {
+    LoudnessPlan lp;
+    int st;
+    if ((st = loudness_plan_checked(sr, L, &lp))) return st;
+    if (!res || C == 0) return invalid("dsp_loudness: needs res and C >= 1");
+    if (flags & ~DSP_LOUDNESS_TRUE_PEAK) return invalid("dsp_loudness: unknown flags");
+    if (goff_of(ex) != 0) return invalid("dsp_loudness: whole rows only (sample_offset 0)");
+    if ((st = check_rows("in", in, C))) return st;
+    if (lp.hops && hop_energy)
+        for (uint32_t c = 0; c < C; ++c)
+            if (!hop_energy[c]) return invalid("hop_energy[%u] is NULL", c);
+    const bool want_tp = (flags & DSP_LOUDNESS_TRUE_PEAK) != 0;
+    const bool run_tp = want_tp && lp.oversample > 1 && L > 0;
+    ResamplePlan rp;
+    if (want_tp && (st = resample_plan_checked(sr, sr * lp.oversample, L, tp_spec, &rp))) return st;  // (the spec's ranges)
+    hipStream_t s = stream_of(ex);
+    if (capturing(s)) {
+        set_last_error("stream capture: dsp_loudness returns host values and synchronises its stream");
+        return DSP_ERR_INVALID;
+    }
+
+    std::vector<double> z((size_t)C * lp.hops, 0.0);
+    std::vector<uint32_t> peaks((size_t)C * 2, 0u);  // per channel: the bits of the sample and of the true peak
+    if (L > 0) {
+        DeviceGuard g(ex);
+        if (g.status) return g.status;
+        Stage stage(ex);
+        const std::vector<const float *> din = stage.in_rows(in, C, L);
+        if (stage.status) return stage.status;
+        DevTable ktab, ttab;  // held until the call's launches are enqueued
+        {
+            // (an eleventh float: never a BIQUAD cascade's key, whose tables differ)
+            std::vector<float> key(lp.kcoef, lp.kcoef + 10);
+            key.push_back(0.f);
+            std::lock_guard<std::mutex> lk(g_mu);
+            const CachedTable *it = nullptr;
+            st = cached_table(g_res[g.dev].iir, key, g.dev, s, "the K-weighting cascade's state-transition tables",
+                              [&](std::vector<float> &h, CachedTable &) { loudness_tables(lp.kcoef, h); }, &it);
+            if (st) return st;
+            ktab = it->dev;
+        }
+        ResampleArgs R{};
+        if (run_tp) {
+            R.L = L;
+            R.Lout = rp.Lout;
+            R.up = rp.up;
+            R.down = rp.down;
+            R.half = rp.half;
+            R.Tp = rp.taps;
+            resample_blocking(&R);
+            // up = ovs, down = 1: one group of ovs phases whose windows coincide, table[step][phase]
+            if (!R.phase || R.R != lp.oversample || R.S != ((rp.taps + 3) & ~3u)) {
+                set_last_error("dsp_loudness: unexpected blocking of the oversampling filter");
+                return DSP_ERR_UNSUPPORTED;
+            }
+            if ((st = resample_cached_table(rp, R, g.dev, s, &ttab))) return st;
+        }
+        float *scratch = nullptr;
+        if ((st = get_scratch(g.dev, s, lp.scratch_bytes, &scratch, 3))) return st;
+        LoudnessArgs A{};
+        A.L = L;
+        A.tiles = lp.tiles;
+        A.hop = lp.hop;
+        A.hops = lp.hops;
+        A.coef = ktab.get();
+        A.Q = A.coef + 20;
+        A.P = A.Q + (size_t)65 * 16;
+        A.window = lp.window;
+        A.run = lp.run;
+        A.z = (double *)scratch;
+        A.peaks = (uint32_t *)(A.z + (size_t)kLoudGroup * lp.hops);
+        A.part = (float *)(A.peaks + 2 * kLoudGroup);
+        st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
+            LoudnessArgs G = A;
+            G.in_aligned16 = 1;
+            for (uint32_t j = 0; j < cn; ++j) {
+                G.in.p[j] = din[c0 + j];
+                if (!aligned(din[c0 + j], 16)) G.in_aligned16 = 0;
+            }
+            DSPB_HIP(hipMemsetAsync(G.peaks, 0, 2 * kLoudGroup * sizeof(uint32_t), s));
+            int e = for_pairs_then_rest(cn, true, [&](uint32_t first, uint32_t count, uint32_t nch) {
+                LoudnessArgs K = G;
+                K.first = first;
+                K.count = count;
+                return launch_loudness_kweight(K, nch, s);
+            });
+            if (e) return e;
+            if ((e = launch_loudness_finish(G, cn, s))) return e;
+            if (run_tp && (e = launch_loudness_truepeak(G, cn, lp.oversample, ttab.get(), R.S, rp.half, s))) return e;
+            for (uint32_t j = 0; j < cn; ++j) {
+                if (lp.hops)
+                    DSPB_HIP(hipMemcpyAsync(z.data() + (size_t)(c0 + j) * lp.hops, G.z + (size_t)j * lp.hops,
+                                            lp.hops * sizeof(double), hipMemcpyDeviceToHost, s));
+                DSPB_HIP(hipMemcpyAsync(&peaks[2 * (size_t)(c0 + j)], G.peaks + j, sizeof(uint32_t),
+                                        hipMemcpyDeviceToHost, s));
+                DSPB_HIP(hipMemcpyAsync(&peaks[2 * (size_t)(c0 + j) + 1], G.peaks + kLoudGroup + j, sizeof(uint32_t),
+                                        hipMemcpyDeviceToHost, s));
+            }
+            return (int)DSP_OK;
+        });
+        if (st) return st;
+        DSPB_HIP(hipStreamSynchronize(s));
+    }
+
+    std::vector<const double *> rows(C);
+    for (uint32_t c = 0; c < C; ++c) rows[c] = z.data() + (size_t)c * lp.hops;
+    loudness_gate(rows.data(), C, lp.hops, lp.hop, weights, res);
+    res->sample_peak = 0.0;
+    res->true_peak = want_tp ? 0.0 : std::nan("");
+    for (uint32_t c = 0; c < C; ++c) {
+        float sp, tp;
+        std::memcpy(&sp, &peaks[2 * (size_t)c], 4);
+        std::memcpy(&tp, &peaks[2 * (size_t)c + 1], 4);
+        const double spd = (double)sp, tpd = !want_tp ? std::nan("") : lp.oversample > 1 ? (double)tp : spd;
+        res->sample_peak = std::max(res->sample_peak, spd);
+        if (want_tp) res->true_peak = std::max(res->true_peak, tpd);
+        if (chan_peaks) chan_peaks[2 * c] = spd, chan_peaks[2 * c + 1] = tpd;
+        if (hop_energy && lp.hops) std::memcpy(hop_energy[c], rows[c], lp.hops * sizeof(double));
+    }
+    return DSP_OK;
 }
 
 uint64_t dsp_stft_frame_count(uint64_t L, uint32_t N, uint32_t H) {

@@ -184,6 +184,34 @@ uint64_t biquad_tiles(uint64_t Ly);
 uint32_t biquad_lane_samples();
 // nch = 2: one wavefront per tile of a channel pair (C even), packed math
 int launch_biquad(const BiquadArgs &A, uint32_t sections, uint32_t nch, hipStream_t s);
+// dsp_loudness (loudness.hip): one channel group (<= 16 rows) per call of each
+// launcher.  Scratch rows are the group's (loudness_host.hpp
+// loudness_scratch_bytes): z[16][hops], peaks[32], part[16][tiles][4].
+struct LoudnessArgs {
+    ChanIn in;
+    uint64_t L;            // samples per row
+    uint32_t first, count; // rows [first, first + count) of the group in this launch
+    uint64_t tiles;        // ceil(L / 2048)
+    uint32_t hop;
+    uint64_t hops;
+    const float *coef;     // loudness_tables: 10 of 20 floats,
+    const float *Q;        // 65 4 x 4: M^(T l) in the scan's coordinates,
+    const float *P;        // 2 4 x 4: I, M^(64 T)
+    uint32_t window;       // warm-up tiles before a wave's run (the cascade's look-back)
+    uint32_t run;          // tiles a wave measures
+    float *part;           // per (row, tile): 4 hop partials, the tile's first hop first
+    double *z;             // per (row, hop): the hop energy
+    uint32_t *peaks;       // [16] sample peaks, [16] true peaks: the bits of max |.|
+    uint32_t in_aligned16;
+};
+// partial sums + sample peaks (nch = 2: one wavefront per channel pair, count even)
+int launch_loudness_kweight(const LoudnessArgs &A, uint32_t nch, hipStream_t s);
+// z[row][j] from the partials, rows [0, rows)
+int launch_loudness_finish(const LoudnessArgs &A, uint32_t rows, hipStream_t s);
+// max |y| of the rows at ovs x the rate; table = resample_device_table's layout
+// for up = ovs, down = 1 ([step][phase], `steps` a multiple of 4)
+int launch_loudness_truepeak(const LoudnessArgs &A, uint32_t rows, uint32_t ovs, const float *table,
+                             uint32_t steps, uint32_t half, hipStream_t s);
 int launch_minmax(const float *x, uint64_t n, uint32_t P, float *vmax, float *vmin, hipStream_t s);
 int launch_spectro(const float *mag, uint64_t F, uint32_t K, uint64_t ld, uint32_t P, float *out,
                    hipStream_t s);

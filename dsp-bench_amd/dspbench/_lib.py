@@ -67,6 +67,15 @@ class dsp_resample_spec(C.Structure):
     _fields_ = [("zeros", C.c_uint32), ("beta", C.c_double), ("rolloff", C.c_double)]
 
 
+class dsp_loudness_result(C.Structure):
+    _fields_ = [("integrated", C.c_double), ("range", C.c_double), ("momentary_max", C.c_double),
+                ("short_term_max", C.c_double), ("sample_peak", C.c_double), ("true_peak", C.c_double),
+                ("blocks", C.c_uint64), ("gated_blocks", C.c_uint64)]
+
+
+DSP_LOUDNESS_TRUE_PEAK = 0x1
+DPP = C.POINTER(C.POINTER(C.c_double))
+
 DSP_WAV_FORMAT_PCM = 1
 DSP_WAV_FORMAT_FLOAT = 3
 DSP_WAV_MAX_DATA_CHUNKS = 8
@@ -154,6 +163,12 @@ _SIGS = {
     "dsp_resample_taps": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(dsp_resample_spec), FP, C.c_uint64]),
     "dsp_resample": (C.c_int, [FPP, C.c_uint32, C.c_uint64, FPP, C.c_uint64, C.c_uint32, C.c_uint32,
                                C.POINTER(dsp_resample_spec), C.POINTER(dsp_exec)]),
+    "dsp_loudness_plan": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint32), FP, C.POINTER(C.c_uint64)]),
+    "dsp_loudness_gate": (C.c_int, [DPP, C.c_uint32, C.c_uint64, C.c_uint32, FP, C.POINTER(dsp_loudness_result)]),
+    "dsp_loudness": (C.c_int, [FPP, C.c_uint32, C.c_uint64, C.c_uint32, FP, C.c_uint32,
+                               C.POINTER(dsp_resample_spec), DPP, C.POINTER(C.c_double),
+                               C.POINTER(dsp_loudness_result), C.POINTER(dsp_exec)]),
     "dsp_render_offline": (C.c_int, [FPP, C.c_uint32, C.c_uint64, FPP, C.c_uint32, C.c_uint32,
                                      C.c_float, C.POINTER(dsp_plugin), C.POINTER(dsp_exec)]),
     "dsp_render_loop": (C.c_int, [FPP, C.c_uint32, C.c_uint64, C.c_uint64, FPP, C.c_uint32, C.c_uint32,

@@ -202,6 +202,80 @@ def resample(x, sr_in: int, sr_out: int, zeros=None, beta=None, rolloff=None, st
     return out[:, :lout]
 
 
+def loudness_plan(sr: int, L_: int = 0) -> dict:
+    """dsp_loudness_plan (host only): hop, hops, oversample and the device
+    scratch bytes of a measurement of L_ samples at rate sr."""
+    hop, hops, ovs, sb = C.c_uint32(), C.c_uint64(), C.c_uint32(), C.c_uint64()
+    check(L.lib().dsp_loudness_plan(sr, L_, C.byref(hop), C.byref(hops), C.byref(ovs), None, C.byref(sb)),
+          "dsp_loudness_plan")
+    return {"hop": hop.value, "hops": hops.value, "oversample": ovs.value, "scratch_bytes": sb.value}
+
+
+def k_weighting(sr: int):
+    """The K-weighting cascade at rate sr: float32 [2, 5], rows b0 b1 b2 a1 a2."""
+    k = np.empty((2, 5), np.float32)
+    check(L.lib().dsp_loudness_plan(sr, 0, None, None, None, _fp(k), None), "dsp_loudness_plan")
+    return k
+
+
+def _double_rows(a):
+    t = (C.POINTER(C.c_double) * max(1, a.shape[0]))()
+    for c in range(a.shape[0]):
+        t[c] = C.cast(C.c_void_p(a[c].ctypes.data), C.POINTER(C.c_double))
+    return t
+
+
+def _weights(weights, channels):
+    if weights is None:
+        return None, None
+    w = np.ascontiguousarray(weights, np.float32)
+    assert w.shape == (channels,)
+    return w, _fp(w)
+
+
+_LOUDNESS_FIELDS = ("integrated", "range", "momentary_max", "short_term_max", "sample_peak", "true_peak")
+
+
+def _loudness_dict(res, fields):
+    out = {k: float(getattr(res, k)) for k in fields}
+    out["blocks"], out["gated_blocks"] = int(res.blocks), int(res.gated_blocks)
+    return out
+
+
+def loudness_gate(hop_energy, hop: int, weights=None) -> dict:
+    """dsp_loudness_gate (host only): integrated, range, momentary_max,
+    short_term_max, blocks and gated_blocks from hop energies [C, hops]."""
+    z = np.ascontiguousarray(hop_energy, np.float64)
+    assert z.ndim == 2
+    w, wp = _weights(weights, z.shape[0])
+    res = L.dsp_loudness_result()
+    check(L.lib().dsp_loudness_gate(_double_rows(z), z.shape[0], z.shape[1], hop, wp, C.byref(res)),
+          "dsp_loudness_gate")
+    return _loudness_dict(res, _LOUDNESS_FIELDS[:4])
+
+
+def loudness(x, sr: int, weights=None, true_peak: bool = True, zeros=None, beta=None, rolloff=None,
+             stream=None) -> dict:
+    """Programme loudness of x [C, L] (torch CUDA tensor, or numpy on the host)
+    at rate sr (dsp_loudness): the result fields, `hop_energy` (numpy [C, hops]
+    float64) and `channel_peaks` (numpy [C, 2]: sample, true)."""
+    in_ptrs, ref = _rows(x)
+    channels, L_ = len(in_ptrs), int(x.shape[1])
+    hops = loudness_plan(sr, L_)["hops"]
+    z = np.zeros((channels, hops), np.float64)
+    peaks = np.zeros((channels, 2), np.float64)
+    w, wp = _weights(weights, channels)
+    spec = _resample_spec(zeros, beta, rolloff)
+    res = L.dsp_loudness_result()
+    ex = _exec(ref, 0, stream)
+    check(L.lib().dsp_loudness(chan_table(in_ptrs), channels, L_, sr, wp, L.DSP_LOUDNESS_TRUE_PEAK if true_peak else 0,
+                               C.byref(spec) if spec is not None else None, _double_rows(z),
+                               peaks.ctypes.data_as(C.POINTER(C.c_double)), C.byref(res), C.byref(ex)), "dsp_loudness")
+    out = _loudness_dict(res, _LOUDNESS_FIELDS)
+    out["hop_energy"], out["channel_peaks"] = z, peaks
+    return out
+
+
 def stft_frames(L_: int, N: int, H: int) -> int:
     return int(L.lib().dsp_stft_frame_count(L_, N, H))
 

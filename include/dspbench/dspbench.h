@@ -234,6 +234,94 @@ int dsp_resample_taps(uint32_t sr_in, uint32_t sr_out, const dsp_resample_spec *
 int dsp_resample(const float *const *in, uint32_t C, uint64_t L, float *const *out, uint64_t Lout,
                  uint32_t sr_in, uint32_t sr_out, const dsp_resample_spec *spec, const dsp_exec *ex);
 
+/* Programme loudness (ITU-R BS.1770-4 / EBU R128), loudness range (EBU Tech
+ * 3342) and true peak of C rows of L samples at rate sr.
+ *
+ * Hop and blocks: hop = (sr + 5) / 10 samples (100 ms); hop j holds samples
+ * [j hop, (j + 1) hop); hops = L / hop (a ragged tail takes no part in the
+ * loudness, but it does in the peaks).  Momentary block i is hops i .. i + 3
+ * (400 ms, 75 % overlap): blocks = hops >= 4 ? hops - 3 : 0.  Short-term
+ * block i is hops i .. i + 29 (3 s).  8000 <= sr <= 384000; any other rate is
+ * DSP_ERR_UNSUPPORTED.
+ *
+ * K-weighting: two direct-form-I sections {b0, b1, b2, a1, a2} with
+ * DSP_PLUGIN_BIQUAD's equation, as a cascade, zero initial state; the
+ * coefficients are computed in float64 and rounded once to float:
+ *   stage 1: f0 = 1681.974450955533, G = 3.999843853973347 dB,
+ *            Q = 0.7071752369554196, K = tan(pi f0 / sr), Vh = 10^(G / 20),
+ *            Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2,
+ *            b0 = (Vh + Vb K / Q + K^2) / a0, b1 = 2 (K^2 - Vh) / a0,
+ *            b2 = (Vh - Vb K / Q + K^2) / a0,
+ *            a1 = 2 (K^2 - 1) / a0, a2 = (1 - K / Q + K^2) / a0
+ *   stage 2: f0 = 38.13547087602444, Q = 0.5003270373238773,
+ *            K = tan(pi f0 / sr), a0 = 1 + K / Q + K^2, b = {1, -2, 1},
+ *            a1 = 2 (K^2 - 1) / a0, a2 = (1 - K / Q + K^2) / a0
+ * (at sr = 48000 these are BS.1770-4's table to every printed digit).
+ * Samples must be finite.
+ *
+ * Hop energy: z[c][j] = sum over hop j of y_c[n]^2 (a double: the sum, not the
+ * mean), y_c the K-weighted channel (fp32 on the device, within a bound of
+ * float64; the same bits on every run).
+ *
+ * Gating (BS.1770-4), with weights G_c (NULL: 1 for every channel; a caller
+ * passes 1.41 for surrounds and 0 for LFE):
+ *   w_i = sum_c G_c (z[c][i] + .. + z[c][i + 3]) / (4 hop),
+ *   l_i = -0.691 + 10 log10 w_i;
+ *   absolute gate l_i > -70; relative gate l_i > -0.691 + 10 log10(mean of w
+ *   over the absolute-gated blocks) - 10;
+ *   integrated = -0.691 + 10 log10(mean of w over the blocks that pass both),
+ *   -HUGE_VAL if none does.  momentary_max = max l_i; short_term_max the same
+ *   over the 3 s blocks; both -HUGE_VAL where there is no block.
+ * Range (EBU Tech 3342): the short-term loudness of every 3 s block (hop
+ *   100 ms); keep those above -70, then those above (the mean power of the
+ *   kept ones, in LUFS) - 20; sorted ascending s[0 .. n):
+ *   range = s[(size_t)((n - 1) 0.95 + 0.5)] - s[(size_t)((n - 1) 0.10 + 0.5)],
+ *   0 where n = 0.
+ * Peaks: sample_peak = max over c, n of |x_c[n]|; true_peak = max over c, m of
+ *   |y_c[m]|, y = dsp_resample's definition for sr -> ovs sr with the caller's
+ *   dsp_resample_spec (NULL: the library default), ovs = 4 for sr < 88200,
+ *   2 for sr < 176400, else 1 (then true_peak = sample_peak).  The oversampled
+ *   signal is never stored. */
+typedef struct dsp_loudness_result {
+    double integrated;      /* LUFS */
+    double range;           /* LU */
+    double momentary_max;   /* LUFS */
+    double short_term_max;  /* LUFS */
+    double sample_peak;     /* linear */
+    double true_peak;       /* linear; NaN without DSP_LOUDNESS_TRUE_PEAK */
+    uint64_t blocks;        /* momentary blocks */
+    uint64_t gated_blocks;  /* of them, those that pass both gates */
+} dsp_loudness_result;
+
+#define DSP_LOUDNESS_TRUE_PEAK 0x1u /* dsp_loudness flags: run the oversampled pass */
+
+/* The plan of a measurement (host only, no device): hop, hops and oversample
+ * as above, kcoef = the two sections' ten floats, scratch_bytes = the device
+ * scratch one channel group of 16 takes (kept per stream).  Any out pointer
+ * may be NULL.  DSP_ERR_UNSUPPORTED for a rate outside 8000..384000. */
+int dsp_loudness_plan(uint32_t sr, uint64_t L, uint32_t *hop, uint64_t *hops, uint32_t *oversample,
+                      float kcoef[10], uint64_t *scratch_bytes);
+
+/* Gating, maxima and range from hop energies (host only): hop_energy is C rows
+ * of `hops` doubles.  Fills integrated, range, momentary_max, short_term_max,
+ * blocks and gated_blocks; leaves the peaks alone.  DSP_ERR_INVALID for C = 0,
+ * hop = 0, a NULL row (with hops > 0) or a NULL res. */
+int dsp_loudness_gate(const double *const *hop_energy, uint32_t C, uint64_t hops, uint32_t hop,
+                      const float *weights, dsp_loudness_result *res);
+
+/* Measures C rows of L samples: device rows, or host rows with
+ * DSP_EXEC_HOST_BUFFERS.  hop_energy (optional): host rows, C of `hops`
+ * doubles.  chan_peaks (optional): host double[2 C], sample then true peak per
+ * channel (the true peak NaN without DSP_LOUDNESS_TRUE_PEAK).  *res is exactly
+ * dsp_loudness_gate of the call's own hop energies, plus the peaks.  The call
+ * returns host values: it synchronises its stream, and refuses a stream that
+ * is being captured.  L = 0 or hops < 4 is DSP_OK with integrated -HUGE_VAL.
+ * DSP_ERR_INVALID for C = 0, a NULL row, a NULL res or a non-zero
+ * sample_offset; DSP_ERR_UNSUPPORTED for the rate. */
+int dsp_loudness(const float *const *in, uint32_t C, uint64_t L, uint32_t sr, const float *weights,
+                 uint32_t flags, const dsp_resample_spec *tp_spec, double *const *hop_energy,
+                 double *chan_peaks, dsp_loudness_result *res, const dsp_exec *ex);
+
 /* Test hooks (not for production use).
  * DSP_DEBUG_BIQUAD_SPIN_LIMIT (set): the sleeps a DSP_PLUGIN_BIQUAD look-back
  *   waits for a preceding tile's words before it gives up (value ~0 restores
