@@ -37,7 +37,7 @@ namespace dspb {
 // once and never read back; 2% faster at the headline shape), 16 =
 // non-temporal magnitude stores (slower: 256-byte row pieces need the L2 to
 // merge them), 32 = 4097-bin rows staged through LDS and stored as 16-byte
-// segments (no gain; implies 64), 64 = the older scalar last combine and
+// segments (no gain in the one-frame kernel; implies 64), 64 = the older scalar last combine and
 // (ka, ka + 16) split (default: the packed combine + split_y2, 60 VALU
 // fewer per frame, the same bits)
 enum { kPkNoBarDft = 1, kPkNoBarTw = 2, kPkNoBarSplit = 4, kPkRenderCached = 8, kPkNtMag = 16, kPkMagLds = 32,
@@ -60,7 +60,12 @@ enum { kPkNoBarDft = 1, kPkNoBarTw = 2, kPkNoBarSplit = 4, kPkRenderCached = 8, 
 // 512 = split_y2 stages the row in LDS at the row's 16-byte phase and stores
 // it as aligned 16-byte pieces (16 dwordx4 + <= 7 dwords instead of 65 dwords);
 // with 16, those pieces are non-temporal stores (16 alone: split_y2's
-// dword row stores non-temporal)
+// dword row stores non-temporal).  It lost 3% in the one-frame-per-wave
+// kernel held at the package power cap, where every LDS instruction cost
+// clock (profiles/r01_power_ablation/magstage_ab_clock.txt): that verdict is
+// for that kernel.  A reused run stores its rows this way
+// (store_row_pieces), where it gains
+// (profiles/r08_row_pieces_ab.txt)
 // 128 / 256: ablation only (A/B of what the stores cost): skip the render
 // stores / the magnitude stores of split_y2 (results discarded)
 // default: no scheduling barriers (round 2: 1.0-1.7% faster on the headline,
@@ -244,6 +249,69 @@ __device__ __forceinline__ void store_row_y2(const float (&M)[kPkRowRegs], float
     }
 }
 
+// A row of a reused run as aligned 16-byte pieces: the lane's magnitudes go to
+// the wave's LDS tile in bin order at the row's dword phase a (bin k at
+// lds[k + a], the addresses of split_y2<STAGE>: conflict-free), so that LDS
+// float4 j is the 16-byte-aligned global piece at bins [4j - a, 4j - a + 4);
+// then 16 ds_read_b128 + 16 dwordx4 stores of 1 KiB per wave, and the <= 3 head
+// and <= 3 tail bins as dwords from the registers that hold them (bins 0..2 are
+// M[0], bins 4096..4094 M[2], of lanes 0..2).  The same floats at the same
+// addresses as store_row_y2.  a changes from row to row unless ld % 4 == 0, so
+// every row is staged again; one wave owns the tile (kPkW1), so the fences
+// order its own LDS traffic and no barrier is needed.
+template <bool NT>
+__device__ __forceinline__ void store_row_pieces(const float (&M)[kPkRowRegs], float *mrow, uint32_t lane, float *lds) {
+    const uint32_t a = (uint32_t)(reinterpret_cast<uintptr_t>(mrow) >> 2) & 3u;
+    float *sl = lds + a;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        (sl + lane)[64 * q] = M[4 * q];
+        (sl + 2048u + lane)[64 * q] = M[4 * q + 1];
+        (sl + 4096u - lane)[-64 * q] = M[4 * q + 2];
+        (sl + 2048u - lane)[-64 * q] = M[4 * q + 3];
+    }
+    if (lane == 0) {
+        sl[1024] = M[64];
+        sl[3072] = M[65];
+    }
+    lds_fence();
+    // aligned pieces j in [j0, j1]: bins [4j - a, 4j - a + 4) inside [0, 4097)
+    const uint32_t j0 = a ? 1u : 0u, j1 = (4093u + a) >> 2;
+    float *gb = mrow - a;  // 16-byte aligned
+    float4 p[16];
+#pragma unroll
+    for (int it = 0; it < 16; ++it) {
+        const uint32_t j = j0 + 64u * (uint32_t)it + lane;  // <= 1024: inside the 4160-float tile
+        p[it] = reinterpret_cast<const float4 *>(lds)[j];
+    }
+    lds_fence();  // the next row's LDS writes come after these reads
+#pragma unroll
+    for (int it = 0; it < 16; ++it) {
+        const uint32_t j = j0 + 64u * (uint32_t)it + lane;
+        if (it < 15 || j <= j1)
+            st<NT>(reinterpret_cast<f4a *>(gb + 4u * j), f4a{p[it].x, p[it].y, p[it].z, p[it].w});
+    }
+    // head bins [0, 4 j0 - a) and tail bins [4 j1 + 4 - a, 4097)
+    const uint32_t head = 4u * j0 - a, tail0 = 4u * j1 + 4u - a;
+    if (lane < head) mrow[lane] = M[0];
+    if (4096u - lane >= tail0) (mrow + 4096u - lane)[0] = M[2];
+}
+
+// The stores of a reused run (REUSE, nrun > 1), measured in
+// profiles/r08_row_pieces_ab.txt.  Rows: 0 = store_row_y2's dwords, 1 = aligned
+// 16-byte pieces (store_row_pieces), 2 = those pieces non-temporal.  Render
+// first: all the run's hops are stored right after the gather, before the
+// window and the FFT, and the samples are not gathered a second time.  (Macros
+// so that A/B builds can set them; the kernel's name does not change.)
+#ifndef DSPB_PK_RUN_ROWS
+#define DSPB_PK_RUN_ROWS 1
+#endif
+#ifndef DSPB_PK_RUN_RENDER_FIRST
+#define DSPB_PK_RUN_RENDER_FIRST 1
+#endif
+constexpr int kPkRunRows = DSPB_PK_RUN_ROWS;
+constexpr bool kPkRunRenderFirst = DSPB_PK_RUN_RENDER_FIRST != 0;
+
 // PER (Ramp, pow2 B <= 4096): the frame's sample pairs repeat every PER
 // values of b (PER = max(1, B / 128)), so only v[0 .. PER) are fetched from
 // the block table -- 4 gathers at B = 512 -- and v[b] = v[b mod PER] is a
@@ -313,8 +381,8 @@ void stft8192_pk_kernel(Stft8kArgs A) {
     constexpr bool SOA = WINC && MK == MapKind::Ramp && PER > 0 && SRC == kSrcRender;
     // frame reuse (A.run > 1; the launch checked H % B == 0, so every frame of
     // the call holds the same samples): wave w owns the frames [w run, w run +
-    // nrun) of its channel -- one gather, window, FFT and split, then nrun
-    // times the stores of a frame; waves run_waves .. render the tail.  The
+    // nrun) of its channel -- one gather, the nrun hops' render stores, window,
+    // FFT and split, then nrun rows; waves run_waves .. render the tail.  The
     // XCD remap hands each XCD consecutive waves, hence consecutive frames.
     constexpr bool REUSE = SOA && KM == kKHalf && OCC == 2 &&
                            !(OPT & (kPkNoReuse | kPkOldSplit | kPkMagLds | kPkMagStage | kPkAbNoRender | kPkAbNoMag | kPkAbNoXpose));
@@ -399,9 +467,17 @@ void stft8192_pk_kernel(Stft8kArgs A) {
         cx2 X[NJ];
         if constexpr (SOA) {
             per_gather<PER>(A, (uint32_t)(A.goff + fs) + 2u * lane, X);
-            // (a reused frame's hops are stored after the FFT, with its rows)
-            if (!(OPT & kPkAbNoRender) && nrun == 1u)
-                per_render_hop<PER, !(OPT & kPkRenderCached)>(A, A.out.p[ch] + fs, lane, X);
+            if constexpr (REUSE && kPkRunRenderFirst) {
+                // every hop of the run now, so that the memory pipe drains
+                // them during the window and the FFT
+                float *o = A.out.p[ch] + fs;
+                for (uint32_t r = 0; r < nrun; ++r, o += A.H)
+                    per_render_hop<PER, !(OPT & kPkRenderCached)>(A, o, lane, X);
+            } else {
+                // (a reused frame's hops are stored after the FFT, with its rows)
+                if (!(OPT & kPkAbNoRender) && nrun == 1u)
+                    per_render_hop<PER, !(OPT & kPkRenderCached)>(A, A.out.p[ch] + fs, lane, X);
+            }
         }
         // w(n) = wa - wb cos(theta n) = wa - u C_b + v S_b per parity, with
         // u = wb cos(theta n0), v = wb sin(theta n0) of the lane's base angle
@@ -545,9 +621,11 @@ void stft8192_pk_kernel(Stft8kArgs A) {
             P, lds, tlo, thp, lane, Y2);
         if constexpr (REUSE) {
             if (nrun > 1u) {
-                // the spectrum once into registers, the samples gathered again
-                // (not held across the FFT), then each frame's stores: what
-                // nrun one-frame waves would have stored, from the same values
+                // the spectrum once into registers, then each frame's row
+                // stores (and its hop, unless the hops went out before the
+                // FFT; the samples are gathered again for them, not held
+                // across the FFT): what nrun one-frame waves would have
+                // stored, from the same values
                 static_assert(64 * 65 >= 4098, "the kept row fits the wave's LDS tile");
                 split_y2<KM, !(OPT & kPkNoBarSplit), false, false, false, true>(Y2, nullptr, A.K, A.tw, lane, lds, lds);
                 float M[kPkRowRegs];  // each lane reads back what it parked (lane 0: and its two extra bins)
@@ -555,13 +633,21 @@ void stft8192_pk_kernel(Stft8kArgs A) {
                 for (int j = 0; j < 64; ++j) M[j] = (lds + lane)[64 * j];
                 M[64] = lds[4096];
                 M[65] = lds[4097];
-                cx2 X[PER >= 2 ? PER / 2 : 1];
-                per_gather<PER>(A, (uint32_t)(A.goff + fs) + 2u * lane, X);
-                float *o = A.out.p[ch] + fs;
+                auto store_row = [&](float *mrow) {
+                    if constexpr (kPkRunRows == 0) store_row_y2<(OPT & kPkNtMag) != 0>(M, mrow, lane);
+                    else store_row_pieces<kPkRunRows == 2 || (OPT & kPkNtMag) != 0>(M, mrow, lane, lds);
+                };
                 float *mrow = A.mag.p[ch] + f * A.ld;
-                for (uint32_t r = 0; r < nrun; ++r, o += A.H, mrow += A.ld) {
-                    per_render_hop<PER, !(OPT & kPkRenderCached)>(A, o, lane, X);
-                    store_row_y2<(OPT & kPkNtMag) != 0>(M, mrow, lane);
+                if constexpr (kPkRunRenderFirst) {  // (the hops went out before the FFT)
+                    for (uint32_t r = 0; r < nrun; ++r, mrow += A.ld) store_row(mrow);
+                } else {
+                    cx2 X[PER >= 2 ? PER / 2 : 1];
+                    per_gather<PER>(A, (uint32_t)(A.goff + fs) + 2u * lane, X);
+                    float *o = A.out.p[ch] + fs;
+                    for (uint32_t r = 0; r < nrun; ++r, o += A.H, mrow += A.ld) {
+                        per_render_hop<PER, !(OPT & kPkRenderCached)>(A, o, lane, X);
+                        store_row(mrow);
+                    }
                 }
                 return;
             }
