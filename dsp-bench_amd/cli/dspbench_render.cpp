@@ -49,9 +49,21 @@
 //                       integrated) / 20) before the encode; a render that
 //                       measures -inf is an error
 //     --true-peak-ceiling DBTP   with --normalize: lower g so that true_peak g
-//                       <= 10^(DBTP / 20).  None of the three with --loop or the
-//                       multi-GPU modes.  --stft's magnitudes are those of the
-//                       render before this gain (the fused render + STFT)
+//                       <= 10^(DBTP / 20): the whole programme is turned down
+//                       until its loudest peak fits, unless --limit is given
+//     --limit           with --normalize and --true-peak-ceiling: g is not
+//                       lowered; the render is scaled by g and then limited in
+//                       place (dsp_limiter at the ceiling, true-peak detector,
+//                       channels linked), so only the milliseconds around each
+//                       peak are turned down.  The result's true peak is measured
+//                       again and what is left above the ceiling is removed by a
+//                       scalar gain, reported as residual_gain.  Prints the JSON
+//                       line, with "limiter": {min_gain, limited, residual_gain}
+//     --limit-lookahead MS   the limiter's lookahead (1.5; at most 1024 samples)
+//     --limit-release MS     its release time constant (100; 0: none)
+//                       None of these with --loop or the multi-GPU modes.
+//                       --stft's magnitudes are those of the render before this
+//                       gain (the fused render + STFT)
 //     --loop NBLOCKS    loop mode (audio.cpp:100-132): NBLOCKS blocks from a
 //                       file that wraps around (no --stft)
 //   multi-GPU (cfg 5, shard.h): one process per GPU, channels sharded one
@@ -120,7 +132,8 @@ void usage() {
                  "       [--convolve IR.wav] [--gain G] [--ir G,STEP] [--block B] [--bits 16|24|32|float] [--stft MAG.f32]"
                  " [--device N]\n"
                  "       [--device-channels C] [--device-rate R] [--rate R] [--loop NBLOCKS]\n"
-                 "       [--loudness] [--normalize LUFS [--true-peak-ceiling DBTP]]\n"
+                 "       [--loudness] [--normalize LUFS [--true-peak-ceiling DBTP [--limit]]]\n"
+                 "       [--limit-lookahead MS] [--limit-release MS]\n"
                  "       [--world W --rank R --comm-id FILE [--run-id STR] [--chunk SAMPLES]]\n");
 }
 
@@ -189,15 +202,16 @@ int main(int argc, char **argv) {
     uint64_t loop_blocks = 0, chunk = 16ull << 20;
     bool have_rank = false;
     bool want_loudness = false, want_normalize = false, want_ceiling = false;
-    double norm_lufs = 0.0, ceiling_dbtp = 0.0;
+    bool want_limit = false;
+    double norm_lufs = 0.0, ceiling_dbtp = 0.0, limit_lookahead_ms = 1.5, limit_release_ms = 100.0;
     std::string comm_path, run_id;
     const time_t started = std::time(nullptr) - 2;  // (mtime has one-second resolution)
     if (const char *e = std::getenv("DSPB_RUN_ID")) run_id = e;
     else if (const char *e2 = std::getenv("TORCHELASTIC_RUN_ID")) run_id = e2;
-    for (int i = 3; i < argc; i += 2) {  // every option but --loudness takes one value
+    for (int i = 3; i < argc; i += 2) {  // every option but --loudness and --limit takes one value
         const std::string a = argv[i];
-        if (a == "--loudness") {
-            want_loudness = true;
+        if (a == "--loudness" || a == "--limit") {
+            (a == "--limit" ? want_limit : want_loudness) = true;
             --i;
             continue;
         }
@@ -226,7 +240,8 @@ int main(int argc, char **argv) {
                 usage();
                 return 2;
             }
-        } else if (a == "--normalize" || a == "--true-peak-ceiling") {
+        } else if (a == "--normalize" || a == "--true-peak-ceiling" || a == "--limit-lookahead" ||
+                   a == "--limit-release") {
             char *end = nullptr;
             const double val = std::strtod(v, &end);
             if (end == v || *end) {  // not a number
@@ -234,7 +249,9 @@ int main(int argc, char **argv) {
                 return 2;
             }
             if (a == "--normalize") norm_lufs = val, want_normalize = true;
-            else ceiling_dbtp = val, want_ceiling = true;
+            else if (a == "--true-peak-ceiling") ceiling_dbtp = val, want_ceiling = true;
+            else if (a == "--limit-lookahead") limit_lookahead_ms = val;
+            else limit_release_ms = val;
         }
         else if (a == "--loop") loop_blocks = std::strtoull(v, nullptr, 10);
         else if (a == "--world") world = (uint32_t)std::strtoul(v, nullptr, 10);
@@ -261,14 +278,23 @@ int main(int argc, char **argv) {
         usage();
         return 2;
     }
-    if ((want_loudness || want_normalize || want_ceiling) && (loop_blocks || multi || world)) {
-        std::fprintf(stderr, "dspbench_render: --loudness, --normalize and --true-peak-ceiling exclude --loop and the "
-                             "multi-GPU modes\n");
+    if ((want_loudness || want_normalize || want_ceiling || want_limit) && (loop_blocks || multi || world)) {
+        std::fprintf(stderr, "dspbench_render: --loudness, --normalize, --true-peak-ceiling and --limit exclude --loop "
+                             "and the multi-GPU modes\n");
         usage();
         return 2;
     }
     if (want_ceiling && !want_normalize) {
         std::fprintf(stderr, "dspbench_render: --true-peak-ceiling needs --normalize\n");
+        usage();
+        return 2;
+    }
+    if (want_limit && !(want_normalize && want_ceiling)) {
+        std::fprintf(stderr, "dspbench_render: --limit needs --normalize and --true-peak-ceiling\n");
+        usage();
+        return 2;
+    }
+    if (want_limit && !(limit_lookahead_ms >= 0.0 && limit_release_ms >= 0.0)) {
         usage();
         return 2;
     }
@@ -526,7 +552,8 @@ int main(int argc, char **argv) {
         if ((st = dsp_loudness(dout.data(), C, Lr, rate, nullptr, DSP_LOUDNESS_TRUE_PEAK, nullptr, nullptr, nullptr, &lr,
                                &ex)))
             return fail("dsp_loudness", st);
-        float g = 1.f;
+        float g = 1.f, residual = 1.f;
+        dsp_limiter_result lim{};
         if (want_normalize) {
             if (!std::isfinite(lr.integrated)) {
                 std::fprintf(stderr, "dspbench_render: --normalize: the render's integrated loudness is %s "
@@ -534,23 +561,52 @@ int main(int argc, char **argv) {
                 return 1;
             }
             g = (float)std::pow(10.0, (norm_lufs - lr.integrated) / 20.0);
-            if (want_ceiling) {
+            // the largest gain <= g0 that keeps `peak` at or below the ceiling
+            auto fit = [&](double peak, float g0) {
                 const double limit = std::pow(10.0, ceiling_dbtp / 20.0);
-                if (lr.true_peak * (double)g > limit) {
-                    g = (float)(limit / lr.true_peak);
-                    while (g > 0.f && lr.true_peak * (double)g > limit) g = std::nextafterf(g, 0.f);
+                if (peak * (double)g0 > limit) {
+                    g0 = (float)(limit / peak);
+                    while (g0 > 0.f && peak * (double)g0 > limit) g0 = std::nextafterf(g0, 0.f);
                 }
+                return g0;
+            };
+            auto scale = [&](float by) {
+                for (uint32_t c = 0; c < C; ++c)
+                    if (int e = dsp_gain(dout[c], dout[c], by, Lr, &ex)) return e;
+                return 0;
+            };
+            if (want_ceiling && !want_limit) g = fit(lr.true_peak, g);
+            if ((st = scale(g))) return fail("dsp_gain", st);
+            if (want_limit) {
+                // the level stays: the limiter turns down the peaks, then a scalar gain takes what is
+                // left of the true peak above the ceiling (the limiter's gain moves between samples)
+                dsp_limiter_spec ls{};
+                ls.ceiling = (float)std::pow(10.0, ceiling_dbtp / 20.0);
+                const double la = std::floor(limit_lookahead_ms * 1e-3 * (double)rate + 0.5);
+                ls.lookahead = (uint32_t)(la < 1024.0 ? la : 1024.0);
+                ls.release = limit_release_ms * 1e-3 * (double)rate;
+                if (ls.release > 0.0 && ls.release < 1.0) ls.release = 1.0;
+                ls.flags = DSP_LIMITER_TRUE_PEAK;
+                if ((st = dsp_limiter(dout.data(), C, Lr, dout.data(), rate, &ls, nullptr, nullptr, nullptr, &lim, &ex)))
+                    return fail("dsp_limiter", st);
+                dsp_loudness_result after{};
+                if ((st = dsp_loudness(dout.data(), C, Lr, rate, nullptr, DSP_LOUDNESS_TRUE_PEAK, nullptr, nullptr,
+                                       nullptr, &after, &ex)))
+                    return fail("dsp_loudness", st);
+                residual = fit(after.true_peak, 1.f);
+                if (residual != 1.f && (st = scale(residual))) return fail("dsp_gain", st);
             }
-            for (uint32_t c = 0; c < C; ++c)
-                if ((st = dsp_gain(dout[c], dout[c], g, Lr, &ex))) return fail("dsp_gain", st);
         }
-        if (want_loudness) {
+        if (want_loudness || want_limit) {
             std::string j = "{\"integrated\": " + json_num(lr.integrated) + ", \"range\": " + json_num(lr.range) +
                             ", \"momentary_max\": " + json_num(lr.momentary_max) + ", \"short_term_max\": " +
                             json_num(lr.short_term_max) + ", \"sample_peak\": " + json_num(lr.sample_peak) +
                             ", \"true_peak\": " + json_num(lr.true_peak) + ", \"blocks\": " +
                             std::to_string(lr.blocks) + ", \"gated_blocks\": " + std::to_string(lr.gated_blocks);
             if (want_normalize) j += ", \"gain\": " + json_num((double)g);
+            if (want_limit)
+                j += ", \"limiter\": {\"min_gain\": " + json_num(lim.min_gain) + ", \"limited\": " +
+                     std::to_string(lim.limited) + ", \"residual_gain\": " + json_num((double)residual) + "}";
             std::printf("%s}\n", j.c_str());
         }
     }

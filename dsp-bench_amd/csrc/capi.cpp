@@ -23,6 +23,7 @@
 #include "host_hip.hpp"
 #include "host_tables.hpp"
 #include "kernels.hpp"
+#include "limiter_host.hpp"
 #include "loudness_host.hpp"
 #include "dspbench/wav.h"
 
@@ -103,6 +104,7 @@ struct DeviceRes {
     TableCache iir;                                            // biquad cascades seen (plugin_map)
     TableCache conv;                                           // CONV impulse responses seen (plugin_map)
     TableCache resample;                                       // dsp_resample conversions seen (up, down, spec)
+    TableCache limiter;                                        // dsp_limiter tables seen (rho, lookahead)
     std::map<void *, IirWork> iir_work;                        // per stream
     uint32_t *iir_fb_host = nullptr, *iir_fb_dev = nullptr;  // host-mapped counter of repaired launches
     float *delta = nullptr;  // 2048 floats: 1, 0, 0, ... (compute_IR's impulse, read-only)
@@ -268,7 +270,8 @@ static int set_wincomp(int dev, hipStream_t s, int kind, Stft8kArgs *A) {
 // Stream-ordered scratch: calls on one stream are serialised by the stream,
 // so one buffer per (device, stream, slot) is enough.  Slots: 0 the IR_test
 // block table, 1 loop mode's wrapped file, 2 a CONV channel group's spectra,
-// 3 a dsp_loudness channel group's partial sums, hop energies and peaks.
+// 3 a dsp_loudness channel group's partial sums, hop energies and peaks,
+// 4 a dsp_limiter call's hold rows, tile aggregates, carries and result words.
 static int get_scratch(int dev, hipStream_t s, size_t bytes, float **out, int slot_id = 0) {
     std::lock_guard<std::mutex> lk(g_mu);
     DeviceRes &r = g_res[dev];
@@ -1345,6 +1348,25 @@ int dsp_resample(const float *const *in, uint32_t C, uint64_t L, float *const *o
     return (st = stage.copy_back()) ? st : finish(ex);
 }
 
+// The true-peak detector's table (dsp_loudness, dsp_limiter): dsp_resample's
+// cached device table for sr -> ovs sr, whose blocking must be one group of ovs
+// phases with coinciding windows, table[step][phase], R->S steps
+static int oversampler_table(const ResamplePlan &rp, uint64_t L, uint32_t ovs, int dev, hipStream_t s,
+                             ResampleArgs *R, DevTable *table) {
+    R->L = L;
+    R->Lout = rp.Lout;
+    R->up = rp.up;
+    R->down = rp.down;
+    R->half = rp.half;
+    R->Tp = rp.taps;
+    resample_blocking(R);
+    if (!R->phase || R->R != ovs || R->S != ((rp.taps + 3) & ~3u)) {
+        set_last_error("unexpected blocking of the oversampling filter");
+        return DSP_ERR_UNSUPPORTED;
+    }
+    return resample_cached_table(rp, *R, dev, s, table);
+}
+
 static int loudness_plan_checked(uint32_t sr, uint64_t L, LoudnessPlan *p) {
     const char *why = nullptr;
     if (loudness_plan(sr, L, p, &why) == 0) return DSP_OK;
@@ -1420,21 +1442,7 @@ int dsp_loudness(const float *const *in, uint32_t C, uint64_t L, uint32_t sr, co
             ktab = it->dev;
         }
         ResampleArgs R{};
-        if (run_tp) {
-            R.L = L;
-            R.Lout = rp.Lout;
-            R.up = rp.up;
-            R.down = rp.down;
-            R.half = rp.half;
-            R.Tp = rp.taps;
-            resample_blocking(&R);
-            // up = ovs, down = 1: one group of ovs phases whose windows coincide, table[step][phase]
-            if (!R.phase || R.R != lp.oversample || R.S != ((rp.taps + 3) & ~3u)) {
-                set_last_error("dsp_loudness: unexpected blocking of the oversampling filter");
-                return DSP_ERR_UNSUPPORTED;
-            }
-            if ((st = resample_cached_table(rp, R, g.dev, s, &ttab))) return st;
-        }
+        if (run_tp && (st = oversampler_table(rp, L, lp.oversample, g.dev, s, &R, &ttab))) return st;
         float *scratch = nullptr;
         if ((st = get_scratch(g.dev, s, lp.scratch_bytes, &scratch, 3))) return st;
         LoudnessArgs A{};
@@ -1498,6 +1506,209 @@ int dsp_loudness(const float *const *in, uint32_t C, uint64_t L, uint32_t sr, co
         if (hop_energy && lp.hops) std::memcpy(hop_energy[c], rows[c], lp.hops * sizeof(double));
     }
     return DSP_OK;
+}
+
+// dsp_limiter_plan's checks: the limiter's own, then (TRUE_PEAK at ovs > 1) the oversampler's
+static int limiter_plan_checked(uint32_t sr, uint64_t L, uint32_t C, const dsp_limiter_spec *spec,
+                                const dsp_resample_spec *tp_spec, LimiterPlan *p, ResamplePlan *rp) {
+    const char *why = nullptr;
+    if (const int r = limiter_plan(sr, L, C, spec, p, &why)) {
+        set_last_error("%s", why);
+        return r == 1 ? DSP_ERR_INVALID : DSP_ERR_UNSUPPORTED;
+    }
+    if (spec->flags & DSP_LIMITER_TRUE_PEAK) return resample_plan_checked(sr, sr * p->oversample, L, tp_spec, rp);
+    return DSP_OK;
+}
+
+int dsp_limiter_plan(uint32_t sr, uint64_t L, uint32_t C, const dsp_limiter_spec *spec, const dsp_resample_spec *tp_spec,
+                     uint32_t *groups, uint32_t *oversample, float *rho, float *window, uint64_t *scratch_bytes) {
+    LimiterPlan p;
+    ResamplePlan rp;
+    if (int st = limiter_plan_checked(sr, L, C, spec, tp_spec, &p, &rp)) return st;
+    if (groups) *groups = p.groups;
+    if (oversample) *oversample = p.oversample;
+    if (rho) *rho = p.rho;
+    if (window) limiter_window(p.lookahead, window);
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    return DSP_OK;
+}
+
+// whether rows a[0..na) of la floats and b[0..nb) of lb floats overlap; with
+// `same_ok`, a[c] == b[c] (in place) does not count
+static bool limiter_rows_clash(const float *const *a, uint32_t na, const float *const *b, uint32_t nb, uint64_t n,
+                               bool same_ok, bool self) {
+    for (uint32_t i = 0; i < na; ++i)
+        for (uint32_t j = self ? i + 1 : 0; j < nb; ++j) {
+            if (same_ok && i == j && a[i] == b[j]) continue;
+            const uintptr_t p = reinterpret_cast<uintptr_t>(a[i]), q = reinterpret_cast<uintptr_t>(b[j]);
+            if (p < q + 4 * n && q < p + 4 * n) return true;
+        }
+    return false;
+}
+
+int dsp_limiter(const float *const *in, uint32_t C, uint64_t L, float *const *out, uint32_t sr,
+                const dsp_limiter_spec *spec, const dsp_resample_spec *tp_spec, float *const *gain,
+                float *const *detector, dsp_limiter_result *res, const dsp_exec *ex) {
+    LimiterPlan lp;
+    ResamplePlan rp;
+    int st;
+    if ((st = limiter_plan_checked(sr, L, C, spec, tp_spec, &lp, &rp))) return st;
+    if (goff_of(ex) != 0) return invalid("dsp_limiter: whole rows only (sample_offset 0)");
+    if (L == 0) {  // nothing to read or write: the rows are not looked at
+        if (res) res->min_gain = 1.0, res->limited = 0;
+        return DSP_OK;
+    }
+    if ((st = check_rows("in", in, C)) || (st = check_rows("out", out, C))) return st;
+    const uint32_t G = lp.groups;
+    if (gain && (st = check_rows("gain", gain, G))) return st;
+    if (detector && (st = check_rows("detector", detector, G))) return st;
+    {
+        const float *const *o = out, *const *gr = gain, *const *dr = detector;
+        bool clash = limiter_rows_clash(in, C, o, C, L, true, false) || limiter_rows_clash(o, C, o, C, L, false, true);
+        if (gr) clash = clash || limiter_rows_clash(gr, G, in, C, L, false, false) ||
+                        limiter_rows_clash(gr, G, o, C, L, false, false) || limiter_rows_clash(gr, G, gr, G, L, false, true);
+        if (dr) clash = clash || limiter_rows_clash(dr, G, in, C, L, false, false) ||
+                        limiter_rows_clash(dr, G, o, C, L, false, false) || limiter_rows_clash(dr, G, dr, G, L, false, true);
+        if (gr && dr) clash = clash || limiter_rows_clash(gr, G, dr, G, L, false, false);
+        if (clash) return invalid("dsp_limiter: rows overlap (only out[c] == in[c] is allowed)");
+    }
+    hipStream_t s = stream_of(ex);
+    if (res) {
+        res->min_gain = 1.0;
+        res->limited = 0;
+        if (capturing(s)) {
+            set_last_error("stream capture: dsp_limiter with a result returns host values and synchronises its stream");
+            return DSP_ERR_INVALID;
+        }
+    }
+    DeviceGuard g(ex);
+    if (g.status) return g.status;
+    Stage stage(ex);
+    std::vector<const float *> din(C);
+    std::vector<float *> dout(C);
+    for (uint32_t c = 0; c < C; ++c) {  // (in place stays in place on the device)
+        dout[c] = stage.out(out[c], L);
+        din[c] = stage.host && in[c] != out[c] ? stage.in(in[c], L) : stage.host ? dout[c] : in[c];
+        if (stage.host && in[c] == out[c] && !stage.status)
+            stage.status = stage.copy(dout[c], in[c], L * sizeof(float), hipMemcpyHostToDevice);
+    }
+    std::vector<float *> dgain(G, nullptr), ddet(G, nullptr);
+    if (gain) dgain = stage.out_rows(gain, G, L);
+    if (detector) ddet = stage.out_rows(detector, G, L);
+    if (stage.status) return stage.status;
+
+    DevTable ltab, ttab;  // held until the call's launches are enqueued
+    {
+        std::vector<float> key{lp.rho, (float)lp.lookahead};
+        std::lock_guard<std::mutex> lk(g_mu);
+        const CachedTable *it = nullptr;
+        st = cached_table(g_res[g.dev].limiter, key, g.dev, s, "the limiter's release powers and attack window",
+                          [&](std::vector<float> &h, CachedTable &) { limiter_table(lp, h); }, &it);
+        if (st) return st;
+        ltab = it->dev;
+    }
+    ResampleArgs R{};
+    if (lp.oversample > 1 && (st = oversampler_table(rp, L, lp.oversample, g.dev, s, &R, &ttab))) return st;
+    float *scratch = nullptr;
+    if ((st = get_scratch(g.dev, s, lp.scratch_bytes, &scratch, 4))) return st;
+
+    const uint64_t rowlen = lp.tiles * kLimTile;
+    LimiterArgs A{};
+    A.L = L;
+    A.tiles = lp.tiles;
+    A.A = lp.lookahead;
+    A.wpad = lp.wpad;
+    A.c = spec->ceiling;
+    A.tab = ltab.get();
+    A.h = scratch;
+    A.pmax = lp.chunks > 1 ? scratch + (uint64_t)lp.rows * rowlen : nullptr;
+    A.E = scratch + ((uint64_t)lp.rows + (lp.chunks > 1 ? 1 : 0)) * rowlen;
+    A.carry = A.E + (uint64_t)lp.rows * lp.tiles;
+    // (8-byte aligned: whole tiles before it, then two rows of `tiles` floats per scratch row)
+    uint32_t *words = (uint32_t *)(A.carry + (uint64_t)lp.rows * lp.tiles);
+    A.tp = ttab.get();
+    A.steps = R.S;
+    A.half = rp.half;
+    DSPB_HIP(hipMemsetAsync(words, 0xff, 8, s));
+    DSPB_HIP(hipMemsetAsync(words + 2, 0, 8, s));
+
+    // rows [c0, c0 + cn) as a launch's tables
+    auto rows_of = [&](uint32_t c0, uint32_t cn, LimiterArgs *K) {
+        K->in_aligned16 = K->out_aligned16 = K->gain_aligned16 = 1;
+        for (uint32_t j = 0; j < cn; ++j) {
+            K->in.p[j] = din[c0 + j];
+            K->out.p[j] = dout[c0 + j];
+            if (!aligned(din[c0 + j], 16)) K->in_aligned16 = 0;
+            if (!aligned(dout[c0 + j], 16)) K->out_aligned16 = 0;
+        }
+    };
+    auto group_rows = [&](uint32_t g0, uint32_t gn, LimiterArgs *K) {
+        for (uint32_t j = 0; j < gn; ++j) {
+            K->gain.p[j] = dgain[g0 + j];
+            K->det.p[j] = ddet[g0 + j];
+            if (!aligned(dgain[g0 + j], 16)) K->gain_aligned16 = 0;
+        }
+    };
+    if (G == 1) {
+        // linked: pass 1 once per 16 channels, p combined (max, exact) in the
+        // scratch row before the last launch takes the hold; pass 3 once per 16
+        uint32_t chunk = 0;
+        st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
+            LimiterArgs K = A;
+            rows_of(c0, cn, &K);
+            group_rows(0, 1, &K);
+            K.ngroups = 1;
+            K.nch = cn;
+            const bool last = chunk + 1 == lp.chunks;
+            K.pmode = last ? 0u : chunk == 0 ? 1u : 2u;
+            K.use_pmax = last && lp.chunks > 1;
+            ++chunk;
+            return launch_limiter_detect(K, lp.oversample, s);
+        });
+        if (st) return st;
+        A.ngroups = 1;
+        A.nch = 1;
+        if ((st = launch_limiter_carry(A, s))) return st;
+        st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
+            LimiterArgs K = A;
+            rows_of(c0, cn, &K);
+            K.ngroups = 1;
+            K.nch = cn;
+            if (c0 == 0) {  // the group's gain row and counts: once
+                group_rows(0, 1, &K);
+                K.words = words;
+            }
+            return launch_limiter_apply(K, s);
+        });
+    } else {
+        // unlinked: 16 groups of one channel per launch, the scratch rows reused in stream order
+        st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
+            LimiterArgs K = A;
+            rows_of(c0, cn, &K);
+            group_rows(c0, cn, &K);
+            K.ngroups = cn;
+            K.nch = 1;
+            K.words = words;
+            int e;
+            if ((e = launch_limiter_detect(K, lp.oversample, s))) return e;
+            if ((e = launch_limiter_carry(K, s))) return e;
+            return launch_limiter_apply(K, s);
+        });
+    }
+    if (st) return st;
+    uint32_t w[4] = {0, 0, 0, 0};
+    if (res) DSPB_HIP(hipMemcpyAsync(w, words, sizeof w, hipMemcpyDeviceToHost, s));
+    if ((st = stage.copy_back())) return st;
+    if (res) {
+        DSPB_HIP(hipStreamSynchronize(s));
+        const uint32_t b = (w[0] & 0x80000000u) ? (w[0] & 0x7fffffffu) : ~w[0];
+        float m;
+        std::memcpy(&m, &b, 4);
+        res->min_gain = (double)m;
+        res->limited = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
+        return DSP_OK;
+    }
+    return finish(ex);
 }
 
 uint64_t dsp_stft_frame_count(uint64_t L, uint32_t N, uint32_t H) {

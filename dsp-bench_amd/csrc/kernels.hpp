@@ -212,6 +212,33 @@ int launch_loudness_finish(const LoudnessArgs &A, uint32_t rows, hipStream_t s);
 // for up = ovs, down = 1 ([step][phase], `steps` a multiple of 4)
 int launch_loudness_truepeak(const LoudnessArgs &A, uint32_t rows, uint32_t ovs, const float *table,
                              uint32_t steps, uint32_t half, hipStream_t s);
+// dsp_limiter (limiter.hip): one launch of each pass serves `ngroups` link
+// groups of `nch` rows each (ngroups nch <= 16): group j is rows [j nch,
+// (j + 1) nch) of in / out and row j of the scratch, of gain and of det.
+struct LimiterArgs {
+    ChanIn in;
+    ChanOut out;
+    ChanOut gain, det;     // per group; NULL: not asked for
+    uint64_t L;
+    uint64_t tiles;        // ceil(L / 2048); scratch rows hold tiles 2048 floats
+    uint32_t ngroups, nch;
+    uint32_t A;            // lookahead
+    uint32_t wpad;         // window entries of the table, a multiple of 8
+    float c;               // ceiling
+    const float *tab;      // limiter_host.hpp limiter_table
+    float *h;              // [ngroups][tiles 2048]
+    float *pmax;           // [tiles 2048]: a linked group's p over its earlier launches (or NULL)
+    uint32_t pmode;        // pass 1: 0 whole (p, hold, E); 1 p of these rows to pmax; 2 the same, max with pmax
+    uint32_t use_pmax;     // pass 1, pmode 0: p is combined with pmax
+    float *E, *carry;      // [ngroups][tiles]
+    uint32_t *words;       // [0] min g as an ordered key, [2..3] the count (64 bits); NULL: not counted
+    const float *tp;       // the oversampler's table [step][phase] (or NULL)
+    uint32_t steps, half;
+    uint32_t in_aligned16, out_aligned16, gain_aligned16;
+};
+int launch_limiter_detect(const LimiterArgs &A, uint32_t ovs, hipStream_t s);
+int launch_limiter_carry(const LimiterArgs &A, hipStream_t s);
+int launch_limiter_apply(const LimiterArgs &A, hipStream_t s);
 int launch_minmax(const float *x, uint64_t n, uint32_t P, float *vmax, float *vmin, hipStream_t s);
 int launch_spectro(const float *mag, uint64_t F, uint32_t K, uint64_t ld, uint32_t P, float *out,
                    hipStream_t s);

@@ -74,6 +74,18 @@ class dsp_loudness_result(C.Structure):
 
 
 DSP_LOUDNESS_TRUE_PEAK = 0x1
+
+
+class dsp_limiter_spec(C.Structure):
+    _fields_ = [("ceiling", C.c_float), ("lookahead", C.c_uint32), ("release", C.c_double), ("flags", C.c_uint32)]
+
+
+class dsp_limiter_result(C.Structure):
+    _fields_ = [("min_gain", C.c_double), ("limited", C.c_uint64)]
+
+
+DSP_LIMITER_UNLINKED = 0x1
+DSP_LIMITER_TRUE_PEAK = 0x2
 DPP = C.POINTER(C.POINTER(C.c_double))
 
 DSP_WAV_FORMAT_PCM = 1
@@ -169,6 +181,12 @@ _SIGS = {
     "dsp_loudness": (C.c_int, [FPP, C.c_uint32, C.c_uint64, C.c_uint32, FP, C.c_uint32,
                                C.POINTER(dsp_resample_spec), DPP, C.POINTER(C.c_double),
                                C.POINTER(dsp_loudness_result), C.POINTER(dsp_exec)]),
+    "dsp_limiter_plan": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(dsp_limiter_spec),
+                                   C.POINTER(dsp_resample_spec), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), FP, FP,
+                                   C.POINTER(C.c_uint64)]),
+    "dsp_limiter": (C.c_int, [FPP, C.c_uint32, C.c_uint64, FPP, C.c_uint32, C.POINTER(dsp_limiter_spec),
+                              C.POINTER(dsp_resample_spec), FPP, FPP, C.POINTER(dsp_limiter_result),
+                              C.POINTER(dsp_exec)]),
     "dsp_render_offline": (C.c_int, [FPP, C.c_uint32, C.c_uint64, FPP, C.c_uint32, C.c_uint32,
                                      C.c_float, C.POINTER(dsp_plugin), C.POINTER(dsp_exec)]),
     "dsp_render_loop": (C.c_int, [FPP, C.c_uint32, C.c_uint64, C.c_uint64, FPP, C.c_uint32, C.c_uint32,

@@ -276,6 +276,67 @@ def loudness(x, sr: int, weights=None, true_peak: bool = True, zeros=None, beta=
     return out
 
 
+def _limiter_spec(sr, ceiling_db, lookahead_ms, release_ms, true_peak, linked):
+    """The limiter's spec from decibels and milliseconds: the ceiling linear in
+    float32, the lookahead rounded to whole samples, the release in samples."""
+    flags = (L.DSP_LIMITER_TRUE_PEAK if true_peak else 0) | (0 if linked else L.DSP_LIMITER_UNLINKED)
+    return L.dsp_limiter_spec(float(np.float32(10.0 ** (ceiling_db / 20.0))), int(round(lookahead_ms * 1e-3 * sr)),
+                              release_ms * 1e-3 * sr, flags)
+
+
+def limiter_plan(sr: int, L_: int = 0, channels: int = 1, ceiling_db: float = -1.0, lookahead_ms: float = 1.5,
+                 release_ms: float = 100.0, true_peak: bool = False, linked: bool = True, zeros=None, beta=None,
+                 rolloff=None, spec=None) -> dict:
+    """dsp_limiter_plan (host only): groups, oversample, rho, the attack window
+    (float32 [A + 1]), the ceiling and lookahead it was asked with, and the
+    device scratch bytes.  `spec` (a dsp_limiter_spec) overrides the decibel /
+    millisecond arguments."""
+    sp = spec if spec is not None else _limiter_spec(sr, ceiling_db, lookahead_ms, release_ms, true_peak, linked)
+    tp = _resample_spec(zeros, beta, rolloff)
+    g, ovs, rho, sb = C.c_uint32(), C.c_uint32(), C.c_float(), C.c_uint64()
+    w = np.zeros(min(max(int(sp.lookahead), 0), 1024) + 1, np.float32)
+    check(L.lib().dsp_limiter_plan(sr, L_, channels, C.byref(sp), C.byref(tp) if tp is not None else None, C.byref(g),
+                                   C.byref(ovs), C.byref(rho), _fp(w), C.byref(sb)), "dsp_limiter_plan")
+    return {"groups": g.value, "oversample": ovs.value, "rho": np.float32(rho.value), "window": w,
+            "ceiling": np.float32(sp.ceiling), "lookahead": int(sp.lookahead), "scratch_bytes": sb.value}
+
+
+def limiter(x, sr: int, ceiling_db: float = -1.0, lookahead_ms: float = 1.5, release_ms: float = 100.0,
+            true_peak: bool = False, linked: bool = True, return_gain: bool = False, return_detector: bool = False,
+            out=None, stream=None, zeros=None, beta=None, rolloff=None, spec=None, result: bool = True):
+    """Look-ahead peak limiter over x [C, L] (torch CUDA tensor, or numpy on the
+    host) at rate sr (dsp_limiter).  Returns (y, info): y like x (`out`, which
+    may be x itself: in place), info with `min_gain` and `limited` (when
+    `result`; the call then synchronises), `gain` and `detector` [groups, L]
+    where asked.  `spec` (a dsp_limiter_spec) overrides the decibel /
+    millisecond arguments."""
+    in_ptrs, ref = _rows(x)
+    channels, L_ = len(in_ptrs), int(x.shape[1])
+    sp = spec if spec is not None else _limiter_spec(sr, ceiling_db, lookahead_ms, release_ms, true_peak, linked)
+    groups = channels if sp.flags & L.DSP_LIMITER_UNLINKED else 1
+    if out is None:
+        out = _alloc_like(ref, (channels, L_))
+    out_ptrs, _ = _rows(out)
+    gain = _alloc_like(ref, (groups, L_)) if return_gain else None
+    det = _alloc_like(ref, (groups, L_)) if return_detector else None
+    tp = _resample_spec(zeros, beta, rolloff)
+    res = L.dsp_limiter_result()
+    ex = _exec(ref, 0, stream)
+    check(L.lib().dsp_limiter(chan_table(in_ptrs), channels, L_, chan_table(out_ptrs), sr, C.byref(sp),
+                              C.byref(tp) if tp is not None else None,
+                              chan_table(_rows(gain)[0]) if return_gain else None,
+                              chan_table(_rows(det)[0]) if return_detector else None,
+                              C.byref(res) if result else None, C.byref(ex)), "dsp_limiter")
+    info = {}
+    if result:
+        info["min_gain"], info["limited"] = float(res.min_gain), int(res.limited)
+    if return_gain:
+        info["gain"] = gain
+    if return_detector:
+        info["detector"] = det
+    return out, info
+
+
 def stft_frames(L_: int, N: int, H: int) -> int:
     return int(L.lib().dsp_stft_frame_count(L_, N, H))
 

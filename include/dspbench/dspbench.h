@@ -322,6 +322,78 @@ int dsp_loudness(const float *const *in, uint32_t C, uint64_t L, uint32_t sr, co
                  uint32_t flags, const dsp_resample_spec *tp_spec, double *const *hop_energy,
                  double *chan_peaks, dsp_loudness_result *res, const dsp_exec *ex);
 
+/* Look-ahead peak limiter, offline and zero-latency: C rows of L finite samples
+ * at rate sr come out as C rows of L samples with |y| <= ceiling, no delay.
+ *
+ * Spec: ceiling c > 0 (linear, finite); lookahead A in samples, 0..1024;
+ * release tau in samples, 0 (none) or 1..2^22; flags DSP_LIMITER_*.
+ * Channels form link groups: one group of all C channels, or with
+ * DSP_LIMITER_UNLINKED one group per channel.  Per group:
+ *   1. detector   p[n] = max over the group's channels of |x_c[n]|; with
+ *                 DSP_LIMITER_TRUE_PEAK of max(|x_c[n]|, max_{phi < ovs}
+ *                 |u_c[ovs n + phi]|), u = dsp_resample's y for sr -> ovs sr
+ *                 with the caller's dsp_resample_spec (NULL: the default), ovs
+ *                 as in dsp_loudness (4 / 2 / 1; at 1 the flag changes
+ *                 nothing).  The oversampled signal is never stored.
+ *   2. needed     a[n] = p[n] > c ? 1 - c / p[n] : 0 (fp32, IEEE division);
+ *                 a[n] = 0 for n >= L.
+ *   3. hold       h[n] = max_{n <= j <= n + A} a[j].
+ *   4. release    e[n] = max(h[n], rho e[n - 1]), e[-1] = 0,
+ *                 rho = (float)exp(-1 / tau) (float64, rounded once), 0 for
+ *                 tau = 0.
+ *   5. attack     s[n] = sum_{k = 0..A} w[k] e[n - k], e[j] = 0 for j < 0,
+ *                 w[k] = (float)(v_k / sum v), v_k = sin^2(pi (k + 1) / (A + 2))
+ *                 (float64); A = 0: w = {1}.
+ *   6. output     g[n] = 1 - s[n]; y_c[n] = min(max(x_c[n] g[n], -c), c).
+ * Every e[j], j in [n - A, n], is >= a[n], so in exact arithmetic g[n] <=
+ * c / p[n]: the clamp of step 6 absorbs rounding only, and makes |y| <= c hold
+ * bit for bit.  Where max |x| <= c the call is the identity (g = 1.0f, y = x
+ * bit for bit).  The device's e and s are fp32 within a bound of the float64
+ * definition (the decays of step 4 are powers of rho rounded once, the sum of
+ * step 5 runs k = 0..A in order); the same bits on every run, and for a
+ * prefix of the rows the same bits wherever the definition's are the same.
+ * With a true-peak detector the output's true peak is lowered to about the
+ * ceiling, not guaranteed below it: the gain varies between samples. */
+typedef struct dsp_limiter_spec {
+    float ceiling;      /* linear, > 0 */
+    uint32_t lookahead; /* samples, 0..1024 */
+    double release;     /* samples: 0, or 1..2^22 */
+    uint32_t flags;     /* DSP_LIMITER_* */
+} dsp_limiter_spec;
+
+#define DSP_LIMITER_UNLINKED 0x1u  /* one link group per channel */
+#define DSP_LIMITER_TRUE_PEAK 0x2u /* the oversampled detector */
+
+typedef struct dsp_limiter_result {
+    double min_gain;  /* min over groups and n of g[n]; 1 for L = 0 */
+    uint64_t limited; /* the number of (group, n) with g[n] < 1 */
+} dsp_limiter_result;
+
+/* The plan of a call (host only, no device): link groups, the detector's
+ * oversampling, rho, the window w[0..A] (A + 1 floats) and the bytes of device
+ * scratch the call takes (kept per stream).  Any out pointer may be NULL.
+ * DSP_ERR_INVALID for C = 0, a NULL spec, a ceiling that is not finite and
+ * positive, A > 1024, a release outside its range, unknown flags, or (with
+ * DSP_LIMITER_TRUE_PEAK) a resample spec outside its ranges;
+ * DSP_ERR_UNSUPPORTED with DSP_LIMITER_TRUE_PEAK for what dsp_loudness refuses
+ * (a rate outside 8000..384000). */
+int dsp_limiter_plan(uint32_t sr, uint64_t L, uint32_t C, const dsp_limiter_spec *spec,
+                     const dsp_resample_spec *tp_spec, uint32_t *groups, uint32_t *oversample, float *rho,
+                     float *window, uint64_t *scratch_bytes);
+
+/* Limits C rows of L samples: device rows, or host rows with
+ * DSP_EXEC_HOST_BUFFERS.  out[c] == in[c] (in place) is allowed; any other
+ * overlap between out, in, gain and detector rows is DSP_ERR_INVALID.  gain and
+ * detector (optional): one row of L floats per link group, g[n] and p[n].
+ * ex->sample_offset must be 0.  L = 0 is DSP_OK and writes nothing.  Without
+ * res the call is stream-ordered and does not synchronise; its device table is
+ * cached per device, so a stream being captured needs one eager call of the
+ * same shape first.  With res the call synchronises its stream and refuses a
+ * stream that is being captured.  DSP_ERR_NO_DEVICE without a device. */
+int dsp_limiter(const float *const *in, uint32_t C, uint64_t L, float *const *out, uint32_t sr,
+                const dsp_limiter_spec *spec, const dsp_resample_spec *tp_spec, float *const *gain,
+                float *const *detector, dsp_limiter_result *res, const dsp_exec *ex);
+
 /* Test hooks (not for production use).
  * DSP_DEBUG_BIQUAD_SPIN_LIMIT (set): the sleeps a DSP_PLUGIN_BIQUAD look-back
  *   waits for a preceding tile's words before it gives up (value ~0 restores
