@@ -64,6 +64,19 @@
 //                       None of these with --loop or the multi-GPU modes.
 //                       --stft's magnitudes are those of the render before this
 //                       gain (the fused render + STFT)
+//     --deconvolve REF.wav   swept-sine measurement: IN.wav is the recording, the
+//                       first channel of REF.wav the excitation; OUT.wav is the
+//                       impulse response, one channel per input channel
+//                       (dsp_deconvolve), float unless --bits says otherwise.
+//                       Prints one JSON line: n, eps, pre, ir_length and each
+//                       channel's peak {index, value}.  IN and REF must have the
+//                       same rate.  Not with --plugin, --convolve, --loop,
+//                       --stft, --rate, --loudness, --normalize or the multi-GPU
+//                       modes
+//     --deconv-eps E    the regularisation, 1e-12..1 (1e-6)
+//     --deconv-pre N    output samples of negative time (0): where a sweep's
+//                       harmonic responses land
+//     --ir-length N     samples written (min(n, 2^20): usable by --convolve)
 //     --loop NBLOCKS    loop mode (audio.cpp:100-132): NBLOCKS blocks from a
 //                       file that wraps around (no --stft)
 //   multi-GPU (cfg 5, shard.h): one process per GPU, channels sharded one
@@ -77,6 +90,12 @@
 //                       TORCHELASTIC_RUN_ID, else none: then a file older than
 //                       this process's start is taken as stale and ignored)
 //     --chunk S         pipeline chunk in samples (default 16 Mi)
+//
+// dspbench_render --sweep F1:F2:SECONDS[:RATE[:BITS]] OUT.wav
+//   writes the exponential sine sweep of dsp_sweep (F1..F2 Hz over SECONDS, at
+//   RATE, default 48000, as BITS 16|24|32|float, default float; amplitude 0.5
+//   with 10 ms fades) as a mono WAV: the excitation of a measurement that
+//   --deconvolve evaluates.  Host only: no device is opened.
 #include <hip/hip_runtime.h>
 
 #include <sys/stat.h>
@@ -134,7 +153,9 @@ void usage() {
                  "       [--device-channels C] [--device-rate R] [--rate R] [--loop NBLOCKS]\n"
                  "       [--loudness] [--normalize LUFS [--true-peak-ceiling DBTP [--limit]]]\n"
                  "       [--limit-lookahead MS] [--limit-release MS]\n"
-                 "       [--world W --rank R --comm-id FILE [--run-id STR] [--chunk SAMPLES]]\n");
+                 "       [--deconvolve REF.wav [--deconv-eps E] [--deconv-pre N] [--ir-length N]]\n"
+                 "       [--world W --rank R --comm-id FILE [--run-id STR] [--chunk SAMPLES]]\n"
+                 "       dspbench_render --sweep F1:F2:SECONDS[:RATE[:BITS]] OUT.wav\n");
 }
 
 // rank 0 writes the RCCL id and the run id to `path` (atomically: a temp
@@ -185,15 +206,73 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// --sweep SPEC OUT.wav (either order): the excitation as a mono WAV, host only
+int write_sweep(const char *spec_arg, const char *out_path) {
+    dsp_sweep_spec sp{};
+    sp.amplitude = 0.5;
+    unsigned rate = 48000;
+    char bits_s[8] = "float", tail = 0;
+    const int got = std::sscanf(spec_arg, "%lf:%lf:%lf:%u:%7[a-z0-9]%c", &sp.f1, &sp.f2, &sp.seconds, &rate, bits_s, &tail);
+    const std::string bs = bits_s;
+    if (got < 3 || got > 5 || (bs != "float" && bs != "16" && bs != "24" && bs != "32")) {
+        usage();
+        return 2;
+    }
+    uint64_t L = 0;
+    sp.fade = 0;
+    int st = dsp_sweep_plan(rate, &sp, &L, nullptr);
+    if (st) return fail("dsp_sweep_plan", st);
+    sp.fade = (uint32_t)std::min<uint64_t>(rate / 100, L / 2);  // 10 ms at each end
+    std::vector<float> x(L);
+    if ((st = dsp_sweep(rate, &sp, x.data(), L))) return fail("dsp_sweep", st);
+    const uint16_t fmt = bs == "float" ? DSP_WAV_FORMAT_FLOAT : DSP_WAV_FORMAT_PCM;
+    const uint16_t bits = bs == "float" ? 32 : (uint16_t)std::atoi(bits_s);
+    const size_t bps = bits / 8u;
+    std::vector<unsigned char> out(64 + L * bps);
+    const int hdr = dsp_wav_write_header(out.data(), out.size(), fmt, 1, rate, bits, L);
+    if (hdr < 0) return fail("dsp_wav_write_header", hdr);
+    for (uint64_t i = 0; i < L; ++i) {  // dsp_wav_encode's rounding, on the host
+        uint32_t w;
+        if (fmt == DSP_WAV_FORMAT_FLOAT) std::memcpy(&w, &x[i], 4);
+        else if (bits == 32) {
+            const double r = std::min(std::max(std::rint((double)x[i] * 2147483648.0), -2147483648.0), 2147483647.0);
+            w = (uint32_t)(int32_t)r;
+        } else {
+            const float S = bits == 16 ? 32768.f : 8388608.f;
+            w = (uint32_t)(int32_t)std::fmin(std::fmax(std::rint(x[i] * S), -S), S - 1.f);
+        }
+        for (size_t b = 0; b < bps; ++b) out[hdr + i * bps + b] = (unsigned char)(w >> (8 * b));
+    }
+    FILE *f = std::fopen(out_path, "wb");
+    if (!f || std::fwrite(out.data(), 1, hdr + L * bps, f) != hdr + L * bps) {
+        std::fprintf(stderr, "dspbench_render: cannot write %s\n", out_path);
+        return 1;
+    }
+    std::fclose(f);
+    std::printf("dspbench_render: sweep %g..%g Hz, %llu frames @ %u Hz -> %s (%s)\n", sp.f1, sp.f2,
+                (unsigned long long)L, rate, out_path, bits_s);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
+    for (int i = 1; i < argc; ++i)
+        if (std::string(argv[i]) == "--sweep") {  // its value and one positional argument, nothing else
+            if (argc != 4 || i > 2) {
+                usage();
+                return 2;
+            }
+            return write_sweep(argv[i + 1], argv[i == 1 ? 3 : 1]);
+        }
     if (argc < 3) {
         usage();
         return 2;
     }
     const char *in_path = argv[1], *out_path = argv[2];
-    std::string plugin = "gain_test", stft_path, bits_opt, conv_path;
+    std::string plugin = "gain_test", stft_path, bits_opt, conv_path, deconv_path;
+    double deconv_eps = 1e-6;
+    uint64_t deconv_pre = 0, ir_length = 0;
     bool have_plugin = false;
     float gain = -1.f, ir_gain = 0.9f, ir_step = 0.002f;
     uint32_t B = 512;
@@ -222,6 +301,16 @@ int main(int argc, char **argv) {
         }
         if (a == "--plugin") plugin = v, have_plugin = true;
         else if (a == "--convolve") conv_path = v;
+        else if (a == "--deconvolve") deconv_path = v;
+        else if (a == "--deconv-eps") deconv_eps = std::strtod(v, nullptr);
+        else if (a == "--deconv-pre") deconv_pre = std::strtoull(v, nullptr, 10);
+        else if (a == "--ir-length") {
+            ir_length = std::strtoull(v, nullptr, 10);
+            if (ir_length == 0) {
+                usage();
+                return 2;
+            }
+        }
         else if (a == "--gain") gain = std::strtof(v, nullptr);
         else if (a == "--ir") {
             if (std::sscanf(v, "%f,%f", &ir_gain, &ir_step) != 2) {
@@ -273,6 +362,18 @@ int main(int argc, char **argv) {
         return 2;
     }
     const bool multi = !comm_path.empty();
+    if (!deconv_path.empty() && (have_plugin || !conv_path.empty() || loop_blocks || multi || world || conv_rate ||
+                                 !stft_path.empty() || want_loudness || want_normalize || want_ceiling || want_limit)) {
+        std::fprintf(stderr, "dspbench_render: --deconvolve excludes --plugin, --convolve, --loop, --stft, --rate, "
+                             "--loudness, --normalize and the multi-GPU modes\n");
+        usage();
+        return 2;
+    }
+    if (deconv_path.empty() && (deconv_pre || ir_length || deconv_eps != 1e-6)) {
+        std::fprintf(stderr, "dspbench_render: --deconv-eps, --deconv-pre and --ir-length need --deconvolve\n");
+        usage();
+        return 2;
+    }
     if (conv_rate && (dev_rate || loop_blocks || multi || world)) {
         std::fprintf(stderr, "dspbench_render: --rate excludes --device-rate, --loop and the multi-GPU modes\n");
         usage();
@@ -372,6 +473,89 @@ int main(int argc, char **argv) {
             din[c] = dnew[c];
         }
         L = Ln;
+    }
+    if (!deconv_path.empty()) {
+        // ---- swept-sine measurement: the recording deconvolved by REF's first channel ----
+        std::vector<unsigned char> rf;
+        if (!read_file(deconv_path.c_str(), rf)) {
+            std::fprintf(stderr, "dspbench_render: cannot read %s\n", deconv_path.c_str());
+            return 1;
+        }
+        dsp_wav_info ri{};
+        if ((st = dsp_wav_parse(rf.data(), rf.size(), &ri))) return fail("dsp_wav_parse (excitation)", st);
+        if (ri.sample_rate != info.sample_rate) {
+            std::fprintf(stderr, "dspbench_render: --deconvolve: %s is at %u Hz, %s at %u Hz\n", deconv_path.c_str(),
+                         ri.sample_rate, in_path, info.sample_rate);
+            return 1;
+        }
+        if (ri.frames == 0 || L == 0 || ri.channels == 0 || ri.channels > 16) {
+            std::fprintf(stderr, "dspbench_render: --deconvolve: an empty recording or excitation\n");
+            return 1;
+        }
+        std::vector<unsigned char> rp(ri.data_bytes);
+        for (uint64_t c = 0, o = 0; c < ri.n_data_chunks; ++c) {
+            std::memcpy(rp.data() + o, rf.data() + ri.data_offset[c], ri.data_size[c]);
+            o += ri.data_size[c];
+        }
+        void *d_ref = nullptr;
+        HIPCK(hipMalloc(&d_ref, rp.size() + 16));
+        HIPCK(hipMemcpyAsync(d_ref, rp.data(), rp.size(), hipMemcpyHostToDevice, s));
+        std::vector<float *> dref(ri.channels);
+        for (uint32_t c = 0; c < ri.channels; ++c) HIPCK(hipMalloc(&dref[c], ri.frames * sizeof(float)));
+        if ((st = dsp_wav_decode(d_ref, &ri, 0, ri.frames, dref.data(), &ex))) return fail("dsp_wav_decode", st);
+        uint32_t n = 0;
+        if ((st = dsp_deconv_plan(L, ri.frames, Cf, &n, nullptr))) return fail("dsp_deconv_plan", st);
+        const uint64_t irl = ir_length ? ir_length : std::min<uint64_t>(n, 1u << 20);
+        if (irl > n || deconv_pre > irl) {
+            std::fprintf(stderr, "dspbench_render: --deconvolve: needs --deconv-pre <= --ir-length <= n = %u\n", n);
+            return 2;
+        }
+        std::vector<float *> dir(Cf);
+        for (uint32_t c = 0; c < Cf; ++c) HIPCK(hipMalloc(&dir[c], irl * sizeof(float)));
+        dsp_deconv_spec ds{};
+        ds.eps = deconv_eps;
+        ds.pre = (uint32_t)deconv_pre;
+        if ((st = dsp_deconvolve(din.data(), Cf, L, dref[0], ri.frames, dir.data(), irl, &ds, &ex)))
+            return fail("dsp_deconvolve", st);
+        uint16_t fmt = DSP_WAV_FORMAT_FLOAT, bits = 32;
+        if (!bits_opt.empty() && bits_opt != "float") fmt = DSP_WAV_FORMAT_PCM, bits = (uint16_t)std::atoi(bits_opt.c_str());
+        const uint64_t out_bytes = irl * Cf * (bits / 8u);
+        void *d_opay = nullptr;
+        HIPCK(hipMalloc(&d_opay, out_bytes + 16));
+        if ((st = dsp_wav_encode(dir.data(), Cf, irl, fmt, bits, d_opay, &ex))) return fail("dsp_wav_encode", st);
+        std::vector<unsigned char> out(64 + out_bytes);
+        const int hdr = dsp_wav_write_header(out.data(), out.size(), fmt, (uint16_t)Cf, info.sample_rate, bits, irl);
+        if (hdr < 0) return fail("dsp_wav_write_header", hdr);
+        HIPCK(hipMemcpyAsync(out.data() + hdr, d_opay, out_bytes, hipMemcpyDeviceToHost, s));
+        std::vector<float> h(irl);
+        std::string j = "{\"n\": " + std::to_string(n) + ", \"eps\": " + json_num(deconv_eps) + ", \"pre\": " +
+                        std::to_string(deconv_pre) + ", \"ir_length\": " + std::to_string(irl) + ", \"peaks\": [";
+        for (uint32_t c = 0; c < Cf; ++c) {  // each channel's peak
+            HIPCK(hipMemcpyAsync(h.data(), dir[c], irl * sizeof(float), hipMemcpyDeviceToHost, s));
+            HIPCK(hipStreamSynchronize(s));
+            uint64_t at = 0;
+            for (uint64_t i = 1; i < irl; ++i)
+                if (std::fabs(h[i]) > std::fabs(h[at])) at = i;
+            j += std::string(c ? ", " : "") + "{\"index\": " + std::to_string(at) + ", \"value\": " +
+                 json_num((double)h[at]) + "}";
+        }
+        std::printf("%s]}\n", j.c_str());
+        FILE *f = std::fopen(out_path, "wb");
+        if (!f || std::fwrite(out.data(), 1, hdr + out_bytes, f) != hdr + out_bytes) {
+            std::fprintf(stderr, "dspbench_render: cannot write %s\n", out_path);
+            return 1;
+        }
+        std::fclose(f);
+        std::printf("dspbench_render: %s deconvolved by %s: %u ch x %llu frames @ %u Hz -> %s (n = %u), %.1f ms end to end\n",
+                    in_path, deconv_path.c_str(), Cf, (unsigned long long)irl, info.sample_rate, out_path, n, ms_since(t0));
+        for (float *q : dir) (void)hipFree(q);
+        for (float *q : dref) (void)hipFree(q);
+        for (float *q : din) (void)hipFree(q);
+        (void)hipFree(d_ref);
+        (void)hipFree(d_opay);
+        (void)hipFree(d_pay);
+        (void)hipStreamDestroy(s);
+        return 0;
     }
     const uint64_t nblocks = loop_blocks ? loop_blocks : (L + B - 1) / B, Lr = nblocks * B;
     for (uint32_t c = 0; c < C; ++c) HIPCK(hipMalloc(&dout[c], Lr * sizeof(float)));

@@ -25,6 +25,7 @@
 #include "kernels.hpp"
 #include "limiter_host.hpp"
 #include "loudness_host.hpp"
+#include "sweep_host.hpp"
 #include "dspbench/wav.h"
 
 namespace dspb {
@@ -105,6 +106,7 @@ struct DeviceRes {
     TableCache conv;                                           // CONV impulse responses seen (plugin_map)
     TableCache resample;                                       // dsp_resample conversions seen (up, down, spec)
     TableCache limiter;                                        // dsp_limiter tables seen (rho, lookahead)
+    TableCache rfft;                                           // dsp_rfft twiddle tables seen (n)
     std::map<void *, IirWork> iir_work;                        // per stream
     uint32_t *iir_fb_host = nullptr, *iir_fb_dev = nullptr;  // host-mapped counter of repaired launches
     float *delta = nullptr;  // 2048 floats: 1, 0, 0, ... (compute_IR's impulse, read-only)
@@ -271,7 +273,8 @@ static int set_wincomp(int dev, hipStream_t s, int kind, Stft8kArgs *A) {
 // so one buffer per (device, stream, slot) is enough.  Slots: 0 the IR_test
 // block table, 1 loop mode's wrapped file, 2 a CONV channel group's spectra,
 // 3 a dsp_loudness channel group's partial sums, hop energies and peaks,
-// 4 a dsp_limiter call's hold rows, tile aggregates, carries and result words.
+// 4 a dsp_limiter call's hold rows, tile aggregates, carries and result words,
+// 5 a dsp_rfft / dsp_irfft / dsp_deconvolve channel group's work buffers and spectra.
 static int get_scratch(int dev, hipStream_t s, size_t bytes, float **out, int slot_id = 0) {
     std::lock_guard<std::mutex> lk(g_mu);
     DeviceRes &r = g_res[dev];
@@ -1709,6 +1712,239 @@ int dsp_limiter(const float *const *in, uint32_t C, uint64_t L, float *const *ou
         return DSP_OK;
     }
     return finish(ex);
+}
+
+int dsp_rfft_plan(uint32_t n, uint32_t *passes, uint32_t radix[4], uint64_t *scratch_bytes_per_channel) {
+    if (!rfft_plan(n, passes, radix)) return invalid("dsp_rfft: n must be a power of two in [2^10, 2^24]");
+    if (scratch_bytes_per_channel) *scratch_bytes_per_channel = rfft_scratch_bytes(n);
+    return DSP_OK;
+}
+
+// the twiddle table of n, cached per device; *hold keeps it until the call's launches are enqueued
+static int rfft_cached_table(uint32_t n, int dev, hipStream_t s, DevTable *hold) {
+    std::vector<float> key{(float)n};  // (a power of two: exact)
+    std::lock_guard<std::mutex> lk(g_mu);
+    const CachedTable *it = nullptr;
+    const int st = cached_table(g_res[dev].rfft, key, dev, s, "the large FFT's twiddle table",
+                                [&](std::vector<float> &h, CachedTable &) { rfft_twiddles(n, h); }, &it);
+    if (st) return st;
+    *hold = it->dev;
+    return DSP_OK;
+}
+
+// a launch's plan, table and the work buffers of `nch` channels at `work`
+static int big_fft_args(uint32_t n, uint32_t nch, const float *table, float *work, BigFftArgs *A) {
+    A->n = n;
+    A->nch = nch;
+    if (!rfft_plan(n, &A->passes, A->radix)) return DSP_ERR_INVALID;
+    A->tw = reinterpret_cast<const v2f *>(table);
+    A->buf0 = reinterpret_cast<v2f *>(work);
+    A->buf1 = A->buf0 + (uint64_t)nch * (n / 2);
+    A->in_aligned8 = A->out_aligned8 = 1;
+    return DSP_OK;
+}
+
+static bool rows_clash_each_other(float *const *rows, uint32_t C, uint64_t n) {
+    for (uint32_t i = 0; i < C; ++i)
+        if (rows_overlap(rows + i, 1, n, rows + i + 1, C - i - 1, n)) return true;
+    return false;
+}
+
+int dsp_rfft(const float *const *in, uint32_t C, uint64_t L, uint32_t n, float *const *spec, const dsp_exec *ex) {
+    int st;
+    if ((st = dsp_rfft_plan(n, nullptr, nullptr, nullptr))) return st;
+    if (L > n) return invalid("dsp_rfft: L %llu > n %u", (unsigned long long)L, n);
+    if (goff_of(ex) != 0) return invalid("dsp_rfft: whole rows only (sample_offset 0)");
+    if (C == 0) return DSP_OK;
+    if ((st = check_rows("spec", spec, C)) || (L && (st = check_rows("in", in, C)))) return st;
+    const uint64_t bins2 = (uint64_t)n + 2;  // floats of a spectrum
+    if ((L && rows_overlap(in, C, L, spec, C, bins2)) || rows_clash_each_other(spec, C, bins2))
+        return invalid("dsp_rfft: spectrum rows overlap input rows or each other");
+    DeviceGuard g(ex);
+    if (g.status) return g.status;
+    hipStream_t s = stream_of(ex);
+    Stage stage(ex);
+    const std::vector<float *> dspec = stage.out_rows(spec, C, bins2);
+    std::vector<const float *> din(C);
+    for (uint32_t c = 0; c < C; ++c) din[c] = L ? stage.in(in[c], L) : dspec[c];  // (L = 0: never read)
+    if (stage.status) return stage.status;
+    DevTable table;
+    if ((st = rfft_cached_table(n, g.dev, s, &table))) return st;
+    const uint32_t rows = std::min<uint32_t>(C, kMaxChannels);
+    float *work = nullptr;
+    if ((st = get_scratch(g.dev, s, rows * rfft_scratch_bytes(n), &work, 5))) return st;
+    st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
+        BigFftArgs A{};
+        if (int e = big_fft_args(n, cn, table.get(), work, &A)) return e;
+        A.L = L;
+        for (uint32_t j = 0; j < cn; ++j) {
+            A.in.p[j] = din[c0 + j];
+            A.out.p[j] = dspec[c0 + j];
+            if (!aligned(din[c0 + j], 8)) A.in_aligned8 = 0;
+            if (!aligned(dspec[c0 + j], 8)) A.out_aligned8 = 0;
+        }
+        return launch_big_rfft(A, s);
+    });
+    if (st) return st;
+    return (st = stage.copy_back()) ? st : finish(ex);
+}
+
+int dsp_irfft(const float *const *spec, uint32_t C, uint32_t n, float *const *out, uint64_t Lout,
+              const dsp_exec *ex) {
+    int st;
+    if ((st = dsp_rfft_plan(n, nullptr, nullptr, nullptr))) return st;
+    if (Lout > n) return invalid("dsp_irfft: Lout %llu > n %u", (unsigned long long)Lout, n);
+    if (goff_of(ex) != 0) return invalid("dsp_irfft: whole rows only (sample_offset 0)");
+    if (C == 0 || Lout == 0) return DSP_OK;
+    if ((st = check_rows("spec", spec, C)) || (st = check_rows("out", out, C))) return st;
+    const uint64_t bins2 = (uint64_t)n + 2;
+    if (rows_overlap(spec, C, bins2, out, C, Lout) || rows_clash_each_other(out, C, Lout))
+        return invalid("dsp_irfft: output rows overlap spectrum rows or each other");
+    DeviceGuard g(ex);
+    if (g.status) return g.status;
+    hipStream_t s = stream_of(ex);
+    Stage stage(ex);
+    const std::vector<const float *> dspec = stage.in_rows(spec, C, bins2);
+    const std::vector<float *> dout = stage.out_rows(out, C, Lout);
+    if (stage.status) return stage.status;
+    DevTable table;
+    if ((st = rfft_cached_table(n, g.dev, s, &table))) return st;
+    const uint32_t rows = std::min<uint32_t>(C, kMaxChannels);
+    float *work = nullptr;
+    if ((st = get_scratch(g.dev, s, rows * rfft_scratch_bytes(n), &work, 5))) return st;
+    st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
+        BigFftArgs A{};
+        if (int e = big_fft_args(n, cn, table.get(), work, &A)) return e;
+        A.Lout = Lout;
+        for (uint32_t j = 0; j < cn; ++j) {
+            A.in.p[j] = dspec[c0 + j];
+            A.out.p[j] = dout[c0 + j];
+            if (!aligned(dspec[c0 + j], 8)) A.in_aligned8 = 0;
+            if (!aligned(dout[c0 + j], 8)) A.out_aligned8 = 0;
+        }
+        return launch_big_irfft(A, s);
+    });
+    if (st) return st;
+    return (st = stage.copy_back()) ? st : finish(ex);
+}
+
+int dsp_deconv_plan(uint64_t Ly, uint64_t Ls, uint32_t C, uint32_t *n, uint64_t *scratch_bytes) {
+    const char *why = nullptr;
+    if (const int r = deconv_plan(Ly, Ls, C, n, scratch_bytes, &why)) {
+        set_last_error("%s", why);
+        return r == 1 ? DSP_ERR_INVALID : DSP_ERR_UNSUPPORTED;
+    }
+    return DSP_OK;
+}
+
+int dsp_deconvolve(const float *const *rec, uint32_t C, uint64_t Ly, const float *ref, uint64_t Ls,
+                   float *const *ir, uint64_t ir_len, const dsp_deconv_spec *spec, const dsp_exec *ex) {
+    int st;
+    uint32_t n = 0;
+    uint64_t scratch_bytes = 0;
+    if ((st = dsp_deconv_plan(Ly, Ls, C, &n, &scratch_bytes))) return st;
+    const double eps = spec ? spec->eps : 1e-6;
+    const uint32_t pre = spec ? spec->pre : 0;
+    if (!std::isfinite(eps) || eps < 1e-12 || eps > 1.0) return invalid("dsp_deconvolve: eps must be in [1e-12, 1]");
+    if (ir_len > n || pre > ir_len)
+        return invalid("dsp_deconvolve: needs pre <= ir_len <= n (%u, %llu, %u)", pre, (unsigned long long)ir_len, n);
+    if (goff_of(ex) != 0) return invalid("dsp_deconvolve: whole rows only (sample_offset 0)");
+    if (!ref) return invalid("ref is NULL");
+    if ((st = check_rows("rec", rec, C)) || (st = check_rows("ir", ir, C))) return st;
+    if (rows_overlap(rec, C, Ly, ir, C, ir_len) || rows_overlap(&ref, 1, Ls, ir, C, ir_len) ||
+        rows_clash_each_other(ir, C, ir_len))
+        return invalid("dsp_deconvolve: ir rows overlap rec, ref or each other");
+    hipStream_t s = stream_of(ex);
+    DeviceGuard g(ex);
+    if (g.status) return g.status;
+    if (capturing(s)) {
+        set_last_error("stream capture: dsp_deconvolve reads the excitation's maximum back and synchronises its stream");
+        return DSP_ERR_INVALID;
+    }
+    Stage stage(ex);
+    const std::vector<const float *> drec = stage.in_rows(rec, C, Ly);
+    const float *dref = stage.in(ref, Ls);
+    const std::vector<float *> dir = stage.out_rows(ir, C, ir_len);
+    if (stage.status) return stage.status;
+    DevTable table;
+    if ((st = rfft_cached_table(n, g.dev, s, &table))) return st;
+    float *scratch = nullptr;
+    if ((st = get_scratch(g.dev, s, scratch_bytes, &scratch, 5))) return st;
+    // [rows][2][M] work, [rows][M + 1] the recordings' spectra, [M + 1] the excitation's, the word of the maximum
+    const uint32_t rows = std::min<uint32_t>(C, kMaxChannels), bins = n / 2 + 1;
+    v2f *Y = reinterpret_cast<v2f *>(scratch) + (uint64_t)rows * n;
+    v2f *S = Y + (uint64_t)rows * bins;
+    uint32_t *word = reinterpret_cast<uint32_t *>(S + bins);
+    DSPB_HIP(hipMemsetAsync(word, 0, 16, s));
+    {
+        BigFftArgs A{};
+        if ((st = big_fft_args(n, 1, table.get(), scratch, &A))) return st;
+        A.L = Ls;
+        A.in.p[0] = dref;
+        A.out.p[0] = reinterpret_cast<float *>(S);
+        A.in_aligned8 = aligned(dref, 8);
+        if ((st = launch_big_rfft(A, s)) || (st = launch_deconv_max(S, bins, word, s))) return st;
+    }
+    uint32_t maxbits = 0;
+    DSPB_HIP(hipMemcpyAsync(&maxbits, word, sizeof maxbits, hipMemcpyDeviceToHost, s));
+    DSPB_HIP(hipStreamSynchronize(s));
+    if (maxbits == 0) return invalid("dsp_deconvolve: the excitation's spectrum is all zeros");
+    if (ir_len) {
+        st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
+            BigFftArgs A{};
+            if (int e = big_fft_args(n, cn, table.get(), scratch, &A)) return e;
+            BigFftArgs B = A;
+            A.L = Ly;
+            B.Lout = ir_len;
+            B.rot = pre & (n - 1);
+            for (uint32_t j = 0; j < cn; ++j) {
+                A.in.p[j] = drec[c0 + j];
+                A.out.p[j] = B.out.p[j] = reinterpret_cast<float *>(Y + (uint64_t)j * bins);
+                if (!aligned(drec[c0 + j], 8)) A.in_aligned8 = 0;
+                B.in.p[j] = A.out.p[j];
+                B.out.p[j] = dir[c0 + j];
+                if (!aligned(dir[c0 + j], 8)) B.out_aligned8 = 0;
+            }
+            int e;
+            if ((e = launch_big_rfft(A, s))) return e;
+            if ((e = launch_deconv_divide(Y, S, bins, cn, (float)eps, word, s))) return e;
+            return launch_big_irfft(B, s);
+        });
+        if (st) return st;
+    }
+    return (st = stage.copy_back()) ? st : finish(ex);
+}
+
+static int sweep_plan_checked(uint32_t sr, const dsp_sweep_spec *spec, SweepPlan *p) {
+    const char *why = nullptr;
+    if (sweep_plan(sr, spec, p, &why) == 0) return DSP_OK;
+    set_last_error("%s", why);
+    return DSP_ERR_INVALID;
+}
+
+int dsp_sweep_plan(uint32_t sr, const dsp_sweep_spec *spec, uint64_t *L, double *rate) {
+    SweepPlan p;
+    if (int st = sweep_plan_checked(sr, spec, &p)) return st;
+    if (L) *L = p.L;
+    if (rate) *rate = p.rate;
+    return DSP_OK;
+}
+
+int dsp_sweep(uint32_t sr, const dsp_sweep_spec *spec, float *out, uint64_t count) {
+    SweepPlan p;
+    if (int st = sweep_plan_checked(sr, spec, &p)) return st;
+    if (count > p.L) return invalid("dsp_sweep: count %llu > L %llu", (unsigned long long)count, (unsigned long long)p.L);
+    if (count && !out) return invalid("out is NULL");
+    sweep_fill(sr, spec, p, out, count);
+    return DSP_OK;
+}
+
+int dsp_sweep_harmonic_offset(uint32_t sr, const dsp_sweep_spec *spec, uint32_t order, double *samples) {
+    SweepPlan p;
+    if (int st = sweep_plan_checked(sr, spec, &p)) return st;
+    if (order == 0) return invalid("dsp_sweep_harmonic_offset: order must be >= 1");
+    if (samples) *samples = sweep_harmonic_offset(sr, p, order);
+    return DSP_OK;
 }
 
 uint64_t dsp_stft_frame_count(uint64_t L, uint32_t N, uint32_t H) {

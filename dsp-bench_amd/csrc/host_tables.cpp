@@ -281,4 +281,51 @@ uint32_t biquad_tables(const float *cf, uint32_t S, uint32_t lane_samples, std::
     return (finite && W <= 192) ? std::max<uint32_t>(W, 1) : 0u;
 }
 
+bool rfft_plan(uint32_t n, uint32_t *passes, uint32_t radix[4]) {
+    if (n < kBigFftMinN || n > kBigFftMaxN || (n & (n - 1))) return false;
+    uint32_t m = 0;  // log2 M
+    while ((2u << m) < n) ++m;
+    const uint32_t p = (m + 5) / 6;
+    uint32_t d = 6 * p - m;  // bits short of p passes of 64: a last pass of 8 takes 3, passes of 32 one each
+    uint32_t bits[4] = {0, 0, 0, 0};
+    for (uint32_t i = 0; i < p; ++i) bits[i] = 6;
+    uint32_t last = p;
+    if (d >= 3) bits[--last] = 3, d -= 3;
+    for (uint32_t i = 0; i < d; ++i) bits[--last] = 5;
+    if (passes) *passes = p;
+    if (radix)
+        for (uint32_t i = 0; i < 4; ++i) radix[i] = bits[i] ? 1u << bits[i] : 0u;
+    return true;
+}
+
+void rfft_twiddles(uint32_t n, std::vector<float> &h) {
+    const uint32_t lo = rfft_twiddle_lo(n), hi = rfft_twiddle_hi(n);
+    h.assign(2 * ((size_t)lo + hi), 0.f);
+    const double w = -2.0 * M_PI / (double)n;
+    for (uint32_t k = 0; k < lo; ++k) {
+        h[2 * k] = (float)std::cos(w * (double)k);
+        h[2 * k + 1] = (float)std::sin(w * (double)k);
+    }
+    for (uint32_t j = 0; j < hi; ++j) {
+        const double a = w * (double)((uint64_t)j << kBigTwShift);
+        h[2 * ((size_t)lo + j)] = (float)std::cos(a);
+        h[2 * ((size_t)lo + j) + 1] = (float)std::sin(a);
+    }
+}
+
+int deconv_plan(uint64_t Ly, uint64_t Ls, uint32_t C, uint32_t *n, uint64_t *scratch_bytes, const char **why) {
+    const char *dummy;
+    if (!why) why = &dummy;
+    if (Ly == 0 || Ls == 0) return *why = "dsp_deconvolve: needs Ly >= 1 and Ls >= 1", 1;
+    if (C == 0) return *why = "dsp_deconvolve: needs C >= 1", 1;
+    const uint64_t len = std::max(Ly, Ls);
+    if (len > kBigFftMaxN) return *why = "dsp_deconvolve: more than 2^24 samples", 2;
+    uint32_t nn = kBigFftMinN;
+    while (nn < len) nn <<= 1;
+    const uint64_t g = std::min<uint32_t>(C, 16);
+    if (n) *n = nn;
+    if (scratch_bytes) *scratch_bytes = g * rfft_scratch_bytes(nn) + (g + 1) * 8ull * (nn / 2 + 1) + 16;
+    return 0;
+}
+
 }  // namespace dspb

@@ -52,6 +52,24 @@ double resample_h(const ResamplePlan &p, double u);
 // table[phi][i] = (float)h(half - 1 - i + phi / up), phi < up, i < taps; row
 // phi at out + phi * row_stride + row_offset (the other floats are left alone)
 void resample_table(const ResamplePlan &p, float *out, uint64_t row_stride, uint64_t row_offset);
+// dsp_rfft / dsp_irfft / dsp_deconvolve (fft_big.hip): n a power of two in
+// [2^10, 2^24]; the M = n / 2 point complex transform runs as 2..4 Stockham
+// passes of radix 64, 32 or 8, largest first
+constexpr uint32_t kBigFftMinN = 1u << 10, kBigFftMaxN = 1u << 24;
+constexpr uint32_t kBigTwShift = 12;  // W_n^K = hi[K >> 12] lo[K & 4095]
+// the plan of n: *passes and radix[0..passes) (the rest 0).  Returns false for an n outside the range.
+bool rfft_plan(uint32_t n, uint32_t *passes, uint32_t radix[4]);
+// device scratch of one channel: two work buffers of M complex
+inline uint64_t rfft_scratch_bytes(uint32_t n) { return 2ull * 8ull * (n / 2); }
+// floats of the twiddle table of n: lo[k] = W_n^k for k < min(n, 4096), then
+// hi[h] = W_n^(4096 h) for h < max(1, n / 4096), interleaved (re, im), float64 rounded once
+inline uint32_t rfft_twiddle_lo(uint32_t n) { return n < (1u << kBigTwShift) ? n : (1u << kBigTwShift); }
+inline uint32_t rfft_twiddle_hi(uint32_t n) { return n >> kBigTwShift ? n >> kBigTwShift : 1u; }
+void rfft_twiddles(uint32_t n, std::vector<float> &h);
+// dsp_deconv_plan's body: n = max(1024, the next power of two >= max(Ly, Ls));
+// the scratch of a call: a group's work buffers and spectra, the excitation's
+// spectrum, 16 bytes of words.  Returns 0, 1 (invalid) or 2 (unsupported) with *why set.
+int deconv_plan(uint64_t Ly, uint64_t Ls, uint32_t C, uint32_t *n, uint64_t *scratch_bytes, const char **why);
 // whether IR_test's `gain -= step` recurrence equals (float)fma(-i, step, gain) for every i < B
 bool ramp_closed_form(float gain, float step, uint32_t B);
 // a cascade's tables for lanes of `lane_samples` samples (iir.hip biquad_lane_samples()); returns W

@@ -239,6 +239,28 @@ struct LimiterArgs {
 int launch_limiter_detect(const LimiterArgs &A, uint32_t ovs, hipStream_t s);
 int launch_limiter_carry(const LimiterArgs &A, hipStream_t s);
 int launch_limiter_apply(const LimiterArgs &A, hipStream_t s);
+// dsp_rfft / dsp_irfft / dsp_deconvolve (fft_big.hip): `nch` <= 16 channels per
+// launch, channel j's work buffers at buf0 / buf1 + j M (M = n / 2 complex).
+struct BigFftArgs {
+    uint32_t n, nch;
+    uint32_t passes, radix[4];   // host_tables.hpp rfft_plan
+    const v2f *tw;               // rfft_twiddles(n): lo, then hi
+    v2f *buf0, *buf1;            // [nch][M] each
+    ChanIn in;                   // forward: real rows of L samples; inverse: spectra of M + 1 bins
+    ChanOut out;                 // forward: spectra of M + 1 bins; inverse: real rows of Lout samples
+    uint64_t L, Lout;
+    uint32_t rot;                // inverse: sample i of the transform is written at (i + rot) mod n
+    uint32_t in_aligned8, out_aligned8;
+};
+// the forward transform of nch rows: pack + passes + real split
+int launch_big_rfft(const BigFftArgs &A, hipStream_t s);
+// the inverse: inverse split + passes + unpack, scaled by 1 / n
+int launch_big_irfft(const BigFftArgs &A, hipStream_t s);
+// *word = max(*word, the bits of max_k |S[k]|^2) over `bins` bins (an integer atomic max; zero the word first)
+int launch_deconv_max(const v2f *S, uint32_t bins, uint32_t *word, hipStream_t s);
+// Y_j[k] = Y_j[k] conj(S[k]) / (|S[k]|^2 + eps *word) for j < nch spectra of `bins` bins at Y + j bins
+int launch_deconv_divide(v2f *Y, const v2f *S, uint32_t bins, uint32_t nch, float eps, const uint32_t *word,
+                         hipStream_t s);
 int launch_minmax(const float *x, uint64_t n, uint32_t P, float *vmax, float *vmin, hipStream_t s);
 int launch_spectro(const float *mag, uint64_t F, uint32_t K, uint64_t ld, uint32_t P, float *out,
                    hipStream_t s);

@@ -4,14 +4,15 @@ All compute runs in libdspbench.so (HIP kernels for gfx950).  See DESIGN.md.
 """
 from ._lib import (DSP_WIN_HAMMING, DSP_WIN_HANN, DSP_WIN_RECT, DspError, LIB_PATH,  # noqa: F401
                    lib)
-from .api import (IR_BUFFER_LENGTH, Plugin, conv_plan, fft_forward, fft_reverse, ir_analysis,  # noqa: F401
+from .api import (IR_BUFFER_LENGTH, Plugin, conv_plan, deconv_plan, deconvolve, fft_forward, fft_reverse, ir_analysis,  # noqa: F401
                   k_weighting, limiter, limiter_plan, loudness, loudness_gate, loudness_plan, minmax_decimate, num_blocks,
                   render_loop, render_offline, render_stft, render_stft_host,
-                  resample, resample_plan, resample_taps, spectrogram_decimate,
-                  stft_frames, stft_magnitude)
+                  resample, resample_plan, resample_taps, irfft, rfft, rfft_plan, spectrogram_decimate,
+                  stft_frames, stft_magnitude, sweep, sweep_harmonic_offset, sweep_plan)
 from . import module, shard, wav  # noqa: F401
 
 __all__ = ["Plugin", "render_offline", "render_loop", "render_stft_host", "minmax_decimate", "spectrogram_decimate", "stft_magnitude", "render_stft", "ir_analysis",
            "fft_forward", "fft_reverse", "conv_plan", "resample", "resample_plan", "resample_taps", "stft_frames", "num_blocks", "lib", "DspError",
            "loudness", "loudness_plan", "loudness_gate", "k_weighting", "limiter", "limiter_plan",
+           "rfft", "irfft", "rfft_plan", "deconvolve", "deconv_plan", "sweep", "sweep_plan", "sweep_harmonic_offset",
            "DSP_WIN_HAMMING", "DSP_WIN_HANN", "DSP_WIN_RECT", "IR_BUFFER_LENGTH", "shard", "wav", "module"]

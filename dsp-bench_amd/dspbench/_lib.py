@@ -86,6 +86,17 @@ class dsp_limiter_result(C.Structure):
 
 DSP_LIMITER_UNLINKED = 0x1
 DSP_LIMITER_TRUE_PEAK = 0x2
+
+
+class dsp_deconv_spec(C.Structure):
+    _fields_ = [("eps", C.c_double), ("pre", C.c_uint32)]
+
+
+class dsp_sweep_spec(C.Structure):
+    _fields_ = [("f1", C.c_double), ("f2", C.c_double), ("seconds", C.c_double), ("amplitude", C.c_double),
+                ("fade", C.c_uint32)]
+
+
 DPP = C.POINTER(C.POINTER(C.c_double))
 
 DSP_WAV_FORMAT_PCM = 1
@@ -187,6 +198,15 @@ _SIGS = {
     "dsp_limiter": (C.c_int, [FPP, C.c_uint32, C.c_uint64, FPP, C.c_uint32, C.POINTER(dsp_limiter_spec),
                               C.POINTER(dsp_resample_spec), FPP, FPP, C.POINTER(dsp_limiter_result),
                               C.POINTER(dsp_exec)]),
+    "dsp_rfft_plan": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "dsp_rfft": (C.c_int, [FPP, C.c_uint32, C.c_uint64, C.c_uint32, FPP, C.POINTER(dsp_exec)]),
+    "dsp_irfft": (C.c_int, [FPP, C.c_uint32, C.c_uint32, FPP, C.c_uint64, C.POINTER(dsp_exec)]),
+    "dsp_deconv_plan": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "dsp_deconvolve": (C.c_int, [FPP, C.c_uint32, C.c_uint64, FP, C.c_uint64, FPP, C.c_uint64,
+                                 C.POINTER(dsp_deconv_spec), C.POINTER(dsp_exec)]),
+    "dsp_sweep_plan": (C.c_int, [C.c_uint32, C.POINTER(dsp_sweep_spec), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "dsp_sweep": (C.c_int, [C.c_uint32, C.POINTER(dsp_sweep_spec), FP, C.c_uint64]),
+    "dsp_sweep_harmonic_offset": (C.c_int, [C.c_uint32, C.POINTER(dsp_sweep_spec), C.c_uint32, C.POINTER(C.c_double)]),
     "dsp_render_offline": (C.c_int, [FPP, C.c_uint32, C.c_uint64, FPP, C.c_uint32, C.c_uint32,
                                      C.c_float, C.POINTER(dsp_plugin), C.POINTER(dsp_exec)]),
     "dsp_render_loop": (C.c_int, [FPP, C.c_uint32, C.c_uint64, C.c_uint64, FPP, C.c_uint32, C.c_uint32,

@@ -337,6 +337,97 @@ def limiter(x, sr: int, ceiling_db: float = -1.0, lookahead_ms: float = 1.5, rel
     return out, info
 
 
+def rfft_plan(n: int) -> dict:
+    """dsp_rfft_plan (host only): the passes and radices of the n / 2 point
+    complex transform behind an n-point real FFT, and the scratch bytes per channel."""
+    p, r, sb = C.c_uint32(), (C.c_uint32 * 4)(), C.c_uint64()
+    check(L.lib().dsp_rfft_plan(n, C.byref(p), r, C.byref(sb)), "dsp_rfft_plan")
+    return {"passes": p.value, "radix": [int(v) for v in r[:p.value]], "scratch_bytes_per_channel": sb.value}
+
+
+def rfft(x, n: int, L_: int | None = None, out=None, stream=None):
+    """numpy's rfft of the rows of x [C, >= L_] zero-padded to n, a power of two
+    in [2^10, 2^24] (dsp_rfft; torch CUDA tensor, or numpy on the host).
+    Returns float32 [C, n + 2]: n / 2 + 1 bins of interleaved (re, im)."""
+    in_ptrs, ref = _rows(x)
+    L_ = int(x.shape[1]) if L_ is None else L_
+    if out is None:
+        out = _alloc_like(ref, (len(in_ptrs), n + 2))
+    out_ptrs, _ = _rows(out)
+    ex = _exec(ref, 0, stream)
+    check(L.lib().dsp_rfft(chan_table(in_ptrs), len(in_ptrs), L_, n, chan_table(out_ptrs), C.byref(ex)), "dsp_rfft")
+    return out
+
+
+def irfft(spec, n: int, Lout: int | None = None, out=None, stream=None):
+    """numpy's irfft of spec [C, n + 2] (n / 2 + 1 bins of interleaved (re, im)),
+    the first Lout (default n) samples (dsp_irfft).  Returns float32 [C, Lout]."""
+    in_ptrs, ref = _rows(spec)
+    Lout = n if Lout is None else Lout
+    if out is None:
+        out = _alloc_like(ref, (len(in_ptrs), max(Lout, 1)))
+    out_ptrs, _ = _rows(out)
+    ex = _exec(ref, 0, stream)
+    check(L.lib().dsp_irfft(chan_table(in_ptrs), len(in_ptrs), n, chan_table(out_ptrs), Lout, C.byref(ex)), "dsp_irfft")
+    return out[:, :Lout]
+
+
+def deconv_plan(Ly: int, Ls: int, channels: int = 1) -> dict:
+    """dsp_deconv_plan (host only): the transform length n and the device scratch bytes."""
+    n, sb = C.c_uint32(), C.c_uint64()
+    check(L.lib().dsp_deconv_plan(Ly, Ls, channels, C.byref(n), C.byref(sb)), "dsp_deconv_plan")
+    return {"n": n.value, "scratch_bytes": sb.value}
+
+
+def deconvolve(rec, ref, ir_len: int | None = None, eps: float | None = None, pre: int = 0, out=None, stream=None):
+    """The impulse responses [C, ir_len] between the excitation ref [Ls] and the
+    recordings rec [C, Ly] by regularised spectral division (dsp_deconvolve;
+    torch CUDA tensors, or numpy on the host).  The first `pre` samples are
+    negative time; ir_len defaults to the plan's n; eps None is the library's 1e-6."""
+    in_ptrs, r = _rows(rec)
+    Ly, Ls = int(rec.shape[1]), int(ref.shape[0])
+    if ir_len is None:
+        ir_len = deconv_plan(Ly, Ls, len(in_ptrs))["n"]
+    if out is None:
+        out = _alloc_like(r, (len(in_ptrs), max(ir_len, 1)))
+    out_ptrs, _ = _rows(out)
+    ref_ptrs, _ = _rows(ref[None, :] if _is_torch(ref) else np.asarray(ref)[None, :])
+    sp = L.dsp_deconv_spec(1e-6 if eps is None else eps, pre)
+    ex = _exec(r, 0, stream)
+    check(L.lib().dsp_deconvolve(chan_table(in_ptrs), len(in_ptrs), Ly, C.cast(C.c_void_p(ref_ptrs[0]), L.FP), Ls,
+                                 chan_table(out_ptrs), ir_len, C.byref(sp) if (eps is not None or pre) else None,
+                                 C.byref(ex)), "dsp_deconvolve")
+    return out[:, :ir_len]
+
+
+def _sweep_spec(f1, f2, seconds, amplitude, fade):
+    return L.dsp_sweep_spec(f1, f2, seconds, amplitude, fade)
+
+
+def sweep_plan(sr: int, f1: float, f2: float, seconds: float, amplitude: float = 1.0, fade: int = 0) -> dict:
+    """dsp_sweep_plan (host only): the sweep's length L = round(seconds sr) and rate ln(f2 / f1) / seconds."""
+    sp = _sweep_spec(f1, f2, seconds, amplitude, fade)
+    n, rate = C.c_uint64(), C.c_double()
+    check(L.lib().dsp_sweep_plan(sr, C.byref(sp), C.byref(n), C.byref(rate)), "dsp_sweep_plan")
+    return {"L": n.value, "rate": rate.value}
+
+
+def sweep(sr: int, f1: float, f2: float, seconds: float, amplitude: float = 1.0, fade: int = 0):
+    """The exponential sine sweep of dsp_sweep (host only): float32 [L]."""
+    sp = _sweep_spec(f1, f2, seconds, amplitude, fade)
+    x = np.empty(sweep_plan(sr, f1, f2, seconds, amplitude, fade)["L"], np.float32)
+    check(L.lib().dsp_sweep(sr, C.byref(sp), _fp(x), x.size), "dsp_sweep")
+    return x
+
+
+def sweep_harmonic_offset(sr: int, f1: float, f2: float, seconds: float, order: int) -> float:
+    """Samples by which harmonic order `order`'s response precedes the linear one after deconvolution."""
+    sp = _sweep_spec(f1, f2, seconds, 1.0, 0)
+    v = C.c_double()
+    check(L.lib().dsp_sweep_harmonic_offset(sr, C.byref(sp), order, C.byref(v)), "dsp_sweep_harmonic_offset")
+    return v.value
+
+
 def stft_frames(L_: int, N: int, H: int) -> int:
     return int(L.lib().dsp_stft_frame_count(L_, N, H))
 

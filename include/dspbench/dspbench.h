@@ -394,6 +394,82 @@ int dsp_limiter(const float *const *in, uint32_t C, uint64_t L, float *const *ou
                 const dsp_limiter_spec *spec, const dsp_resample_spec *tp_spec, float *const *gain,
                 float *const *detector, dsp_limiter_result *res, const dsp_exec *ex);
 
+/* Large real FFT: n a power of two, 2^10 <= n <= 2^24.  in[c] holds L <= n
+ * samples; the rest of the frame is zero and is never read from memory.
+ * spec[c] holds n / 2 + 1 bins as interleaved (re, im) floats in natural order.
+ *   forward  X[k] = sum_j x[j] e^{-2 pi i j k / n}   (unnormalised)
+ *   inverse  x[j] = 1/n sum_k X[k] e^{+2 pi i j k / n}, the first Lout <= n
+ *            samples written; bins 0 and n / 2 use only their real part.
+ * This is numpy's rfft / irfft convention.  It is NOT dsp_fft_forward's
+ * 1 / sqrt(n) in both directions, which stays as the reference-parity service
+ * for n <= 8192.
+ * Method: z[j] = x[2j] + i x[2j+1], an M = n / 2 point complex transform as 2..4
+ * Stockham passes (the plan, a pure function of n: radices 64, 32 and 8,
+ * largest first), then the real split.  Inter-pass twiddles come from a
+ * two-level table W_n^K = hi[K >> 12] lo[K & 4095] computed in float64 and
+ * rounded once, cached per device by n: a stream being captured needs one eager
+ * call of the same n first.  No float atomics, a fixed summation order: the
+ * same bits on every run, and channel c's bits do not depend on C.  Channel
+ * groups of at most 16 run one after another over a scratch kept per stream.
+ * ex->sample_offset must be 0; output rows must not overlap input rows
+ * (DSP_ERR_INVALID); host rows with DSP_EXEC_HOST_BUFFERS; L = 0 gives a zero
+ * spectrum.  DSP_ERR_NO_DEVICE without a device. */
+/* The plan (host only, no device): the pass count, radix[0..passes) (the rest
+ * 0; their product is n / 2) and the scratch bytes per channel.  Any out
+ * pointer may be NULL.  DSP_ERR_INVALID for an n that is no power of two in
+ * [2^10, 2^24]. */
+int dsp_rfft_plan(uint32_t n, uint32_t *passes, uint32_t radix[4], uint64_t *scratch_bytes_per_channel);
+int dsp_rfft(const float *const *in, uint32_t C, uint64_t L, uint32_t n, float *const *spec, const dsp_exec *ex);
+int dsp_irfft(const float *const *spec, uint32_t C, uint32_t n, float *const *out, uint64_t Lout,
+              const dsp_exec *ex);
+
+/* Deconvolution by regularised spectral division: the impulse response between
+ * an excitation ref (one row of Ls samples, used for every channel) and C
+ * recordings rec[c] of Ly samples.  n = max(1024, the next power of two >=
+ * max(Ly, Ls)); beyond 2^24 DSP_ERR_UNSUPPORTED.  With Y_c = rfft_n(rec[c]) and
+ * S = rfft_n(ref):
+ *   lambda   = (float)eps * max_k |S[k]|^2
+ *   H_c[k]   = Y_c[k] conj(S[k]) / (|S[k]|^2 + lambda)
+ *   h_c      = irfft_n(H_c)
+ *   ir[c][i] = h_c[(i - pre) mod n],  i < ir_len,  pre <= ir_len <= n
+ * so the first `pre` output samples are negative time: where the harmonic
+ * responses of a swept-sine measurement land (dsp_sweep_harmonic_offset).
+ * The maximum is an integer atomic max over the bit patterns of the
+ * non-negative |S|^2 (order-preserving, deterministic); the division is one
+ * pointwise launch between the transforms.  A spec of NULL is eps = 1e-6,
+ * pre = 0.  DSP_ERR_INVALID for eps not finite or outside [1e-12, 1], Ly = 0,
+ * Ls = 0, C = 0, pre > ir_len, ir_len > n, a ref whose spectrum is all zeros
+ * (nothing is written), and any overlap of ir rows with rec, ref or each other.
+ * The call reads the maximum back: it synchronises its stream once, and
+ * refuses a stream that is being captured.  ex->sample_offset must be 0. */
+typedef struct dsp_deconv_spec {
+    double eps;   /* 1e-12 .. 1 */
+    uint32_t pre; /* output samples of negative time */
+} dsp_deconv_spec;
+
+/* The plan (host only): n and the bytes of device scratch (kept per stream). */
+int dsp_deconv_plan(uint64_t Ly, uint64_t Ls, uint32_t C, uint32_t *n, uint64_t *scratch_bytes);
+int dsp_deconvolve(const float *const *rec, uint32_t C, uint64_t Ly, const float *ref, uint64_t Ls,
+                   float *const *ir, uint64_t ir_len, const dsp_deconv_spec *spec, const dsp_exec *ex);
+
+/* The excitation: an exponential sine sweep (Farina), host only, float64
+ * rounded once.  With R = ln(f2 / f1), T = seconds, L = round(T sr):
+ *   x[i] = amplitude sin(2 pi f1 T / R (e^{(i / sr) R / T} - 1)),  i < L
+ * times a raised-cosine fade 0.5 - 0.5 cos(pi (i + 0.5) / fade) over `fade`
+ * samples at each end.  Deconvolved by the sweep, the response of harmonic
+ * order m sits T ln(m) / R seconds before the linear one.
+ * DSP_ERR_INVALID unless 0 < f1 < f2 <= sr / 2, seconds > 0, 1 <= L <= 2^24,
+ * 2 fade <= L and amplitude is finite; dsp_sweep also for count > L. */
+typedef struct dsp_sweep_spec {
+    double f1, f2, seconds, amplitude;
+    uint32_t fade;
+} dsp_sweep_spec;
+
+int dsp_sweep_plan(uint32_t sr, const dsp_sweep_spec *spec, uint64_t *L, double *rate /* ln(f2/f1)/T */);
+int dsp_sweep(uint32_t sr, const dsp_sweep_spec *spec, float *out, uint64_t count);
+/* order >= 1; *samples = T ln(order) / R sr */
+int dsp_sweep_harmonic_offset(uint32_t sr, const dsp_sweep_spec *spec, uint32_t order, double *samples);
+
 /* Test hooks (not for production use).
  * DSP_DEBUG_BIQUAD_SPIN_LIMIT (set): the sleeps a DSP_PLUGIN_BIQUAD look-back
  *   waits for a preceding tile's words before it gives up (value ~0 restores
