@@ -1,9 +1,10 @@
-// host_hip.hpp -- host-side idioms shared by the C ABI (capi.cpp) and the
-// plugin module host (module*.cpp): the device guard, the capture predicate
-// and the row-overlap test.
+// host_hip.hpp -- host-side idioms shared by the C ABI (capi.cpp,
+// capi_render.cpp, capi_signal.cpp) and the plugin module host (module*.cpp):
+// the device guard, the capture predicate and the row-overlap predicates.
 #pragma once
 #include "common.hpp"
 
+#pragma GCC visibility push(hidden)
 namespace dspb {
 
 // RAII: make a device current for the call (a negative index: stay), restore
@@ -36,15 +37,39 @@ inline bool capturing(hipStream_t s) {
     return hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
 }
 
-// whether any input row [in[c], in[c] + L) overlaps any output row [out[c'], out[c'] + Lr)
-inline bool rows_overlap(const float *const *in, uint32_t in_ch, uint64_t L, const float *const *out, uint32_t C,
-                         uint64_t Lr) {
-    for (uint32_t a = 0; a < in_ch; ++a)
-        for (uint32_t b = 0; b < C; ++b) {
-            const uintptr_t i0 = reinterpret_cast<uintptr_t>(in[a]), o0 = reinterpret_cast<uintptr_t>(out[b]);
-            if (L && Lr && i0 < o0 + 4 * Lr && o0 < i0 + 4 * L) return true;
+// `count` rows of `floats` floats each: [rows[c], rows[c] + floats).  A set of
+// empty rows overlaps nothing, and its table is not looked at.
+struct Rows {
+    const float *const *rows;
+    uint32_t count;
+    uint64_t floats;
+};
+
+inline bool row_pair_overlaps(const float *p, uint64_t np, const float *q, uint64_t nq) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + 4 * nq && b < a + 4 * np;
+}
+
+// whether any row of a overlaps any row of b; with `same_ok`, a[c] == b[c]
+// (channel c in place) does not count
+inline bool rows_overlap(const Rows &a, const Rows &b, bool same_ok = false) {
+    if (!a.floats || !b.floats) return false;
+    for (uint32_t i = 0; i < a.count; ++i)
+        for (uint32_t j = 0; j < b.count; ++j) {
+            if (same_ok && i == j && a.rows[i] == b.rows[j]) continue;
+            if (row_pair_overlaps(a.rows[i], a.floats, b.rows[j], b.floats)) return true;
         }
     return false;
 }
 
+// whether any two rows of a overlap each other
+inline bool rows_overlap_each_other(const Rows &a) {
+    if (!a.floats) return false;
+    for (uint32_t i = 0; i < a.count; ++i)
+        for (uint32_t j = i + 1; j < a.count; ++j)
+            if (row_pair_overlaps(a.rows[i], a.floats, a.rows[j], a.floats)) return true;
+    return false;
+}
+
 }  // namespace dspb
+#pragma GCC visibility pop

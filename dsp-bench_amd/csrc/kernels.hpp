@@ -1,5 +1,5 @@
 // kernels.hpp -- kernel argument blocks and launchers shared by the HIP
-// translation units and the C ABI (capi.cpp).
+// translation units and the C ABI (capi.cpp, capi_render.cpp, capi_signal.cpp).
 #pragma once
 #include "common.hpp"
 #include "host_tables.hpp"  // kConvHop, kConvSpec4

@@ -483,7 +483,7 @@ int module_render(dsp_module *m, const void *params, uint32_t params_size, const
     // chain's bits (module_render_seg)
     if (!par && !(flags & DSP_EXEC_SERIAL_STATE) && m->has_facts && m->facts.analyzed && m->facts.writes_state &&
         m->state_size > 0 && m->state_size <= kSegMaxState &&
-        !rows_overlap(in, in_ch, L, out, C, A.nblocks * B)) {
+        !rows_overlap(Rows{in, in_ch, L}, Rows{out, C, A.nblocks * B})) {
         SegLearner &W = m->learn;
         if (int st = module_seg_collect(m, false)) return st;
         W.begin(params, params_size, C, B);

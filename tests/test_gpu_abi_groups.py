@@ -1,4 +1,4 @@
-"""The C ABI's channel groups and host-buffer staging (csrc/capi.cpp).
+"""The C ABI's channel groups and host-buffer staging (csrc/capi_impl.hpp, csrc/capi_render.cpp).
 
 Kernels take at most 16 row pointers, so every entry point walks its rows in
 groups of 16 (and FIR / BIQUAD split a group into pairs and an odd last

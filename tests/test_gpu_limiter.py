@@ -121,6 +121,28 @@ def test_detector_true_peak_impulses(torch_cuda, sr):
     assert ru.same_bits(p[0], want)
 
 
+@pytest.mark.parametrize("sr", [48000, 96000])
+def test_detector_is_the_meters_oversampler(torch_cuda, sr):
+    """the limiter's true-peak detector is the meter's
+    oversampler.  For one input the maximum of the linked detector row equals
+    max(sample_peak, true_peak) of dsp_loudness bit for bit (limiter.hip's
+    OVS > 1 branch and loudness.hip's loudness_truepeak_kernel sum the same
+    products in the same order).  The rows cross a tile of both kernels and
+    start one float off 16-byte alignment."""
+    C, Lx = 2, 2048 + 1024 + 37
+    base = torch_cuda.zeros((C, Lx + 3), dtype=torch_cuda.float32, device="cuda")  # rows 16-byte aligned
+    x = base[:, 1:1 + Lx]
+    x.copy_(torch_cuda.from_numpy(np.random.default_rng(sr).uniform(-1, 1, (C, Lx)).astype(np.float32)))
+    assert all(x[c].data_ptr() % 16 == 4 for c in range(C))
+    k = dict(A=0, tau=0, sr=sr, true_peak=True, linked=True)
+    _, info = d.limiter(x, sr, spec=spec_of(k), return_detector=True)
+    p = info["detector"].cpu().numpy()
+    m = d.loudness(x, sr, true_peak=True)
+    assert lu.oversample(sr) > 1 and p.shape == (1, Lx)
+    assert m["true_peak"] > 0.0 and m["sample_peak"] == float(np.abs(x.cpu().numpy()).max())
+    assert float(p.max()) == max(m["sample_peak"], m["true_peak"])
+
+
 @pytest.mark.parametrize("i", [j for j, k in enumerate(lu.CASES) if k["L"] in (2049, 20000)],
                          ids=lambda j: IDS[j])
 def test_division_pinned(torch_cuda, i):
