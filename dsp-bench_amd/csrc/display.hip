@@ -5,7 +5,9 @@
 // s belongs to pixel s * P / n (64-bit here; the reference's u32 product
 // wraps for long files).  Pixel p owns the contiguous samples
 // [ceil(p n / P), ceil((p + 1) n / P)), so one workgroup reduces one pixel's
-// run of samples: a streaming HBM read.
+// run of samples: a streaming HBM read.  A NaN sample is skipped (fmaxf /
+// fminf here, `>` / `<` in the reference); where a pixel's max or min is
+// zero its sign is whichever zero the reduction order met (values equal).
 //
 // spectrogram_decimate: columns of a long STFT for an overview image,
 // out[p][k] = max over the frames of column p of |X_f[k]| (the reference

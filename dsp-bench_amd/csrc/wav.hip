@@ -153,6 +153,8 @@ template <int BITS, bool FLT>
 __device__ __forceinline__ uint32_t float_to_pcm(float x) {
     if constexpr (FLT) {
         return __float_as_uint(x);
+    } else if (x != x) {
+        return 0u;  // NaN encodes to 0 (wav.h), not to the clip's full-scale negative
     } else if constexpr (BITS == 32) {
         double r = rint((double)x * 2147483648.0);
         r = fmin(fmax(r, -2147483648.0), 2147483647.0);

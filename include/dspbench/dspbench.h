@@ -514,7 +514,14 @@ int dsp_render_loop(const float *const *in, uint32_t in_channels, uint64_t L, ui
  * K <= N/2 + 1 for real input (K = N/2 + 1 = 4097 at N = 8192), or K = N
  * for the reference's all-bins layout (dsp.cpp:65; mirror |X[N-k]| = |X[k]|).
  * N = 8192 runs the CDNA4 wave-per-frame kernel; other powers of two <= 8192
- * run the generic LDS kernel. */
+ * run the generic LDS kernel.
+ * Accuracy, here and in dsp_render_stft: per frame max_k |mag - exact| <=
+ * 1e-6 max_k(exact) + 2^-61.  The absolute term is the quiet-frame floor: the
+ * 8192-point kernels take the root of re^2 + im^2 (of a quarter of it at the
+ * self-paired bin N / 4) with the hardware instruction, which reads a denormal
+ * argument as zero, so a magnitude below 2^-62 may be stored as 0 (2^-61
+ * leaves a factor of two).  It matters only to frames whose peak is below
+ * about 2^-41; samples must be finite for the magnitudes to be defined. */
 int dsp_stft_magnitude(const float *const *in, uint32_t C, uint64_t L, uint32_t N,
                        uint32_t H, int32_t window, uint32_t K, float *const *mag,
                        uint64_t ld, const dsp_exec *ex);

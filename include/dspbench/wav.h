@@ -18,7 +18,11 @@
  *                    int24 divides in double by 2^31 - 1, audio.h:66-110).
  *   dsp_wav_encode   GPU: planar float -> interleaved payload (interleave,
  *                    audio.h:123-133); float32 is exact, PCM rounds half to
- *                    even and clips (the reference has no PCM writer).
+ *                    even and clips (the reference has no PCM writer):
+ *                    code = clip(rint(x * 2^(bits-1)), -2^(bits-1),
+ *                    2^(bits-1) - 1), so +-inf clip to full scale and
+ *                    denormals encode to 0.  A NaN sample encodes to 0 at
+ *                    every PCM width (and stays itself in float32).
  *   dsp_wav_write_header  canonical 44-byte RIFF/WAVE header (46 for
  *                    float, with the cbSize field), RIFF sizes clamped to
  *                    0xFFFFFFFF past 4 GiB.

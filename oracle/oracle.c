@@ -642,6 +642,7 @@ void oracle_deinterleave(float *const *dst, const float *src, uint64_t frames, u
 }
 
 static int64_t round_clip(double x, int64_t lo, int64_t hi) {
+    if (x != x) return 0; /* NaN encodes to 0 (wav.h); the cast below is undefined for it */
     double r = nearbyint(x); /* default rounding mode: half to even */
     if (r < (double)lo) r = (double)lo;
     if (r > (double)hi) r = (double)hi;
