@@ -202,6 +202,72 @@ int get_scratch(int dev, hipStream_t s, size_t bytes, float **out, ScratchSlot s
 }
 
 // ---------------------------------------------------------------------------
+// the spectrum rows of the fused IR_test STFT (capi_render.cpp)
+// ---------------------------------------------------------------------------
+// A retired row that nobody holds and no stream still reads leaves the list to
+// serve again (g_mu held): its buffer and its events, all completed.  Rows are
+// recycled, never freed -- hipFree would make the caller wait for the device --
+// so a device holds kSpectrumRows of them plus what was in flight at once.
+static std::shared_ptr<SpectrumRow> spectrum_recycle(DeviceRes &r) {
+    for (size_t i = 0; i < r.spectrum_retired.size(); ++i) {
+        auto &e = r.spectrum_retired[i];
+        bool done = e.use_count() == 1 && hipEventQuery(e->ready) == hipSuccess;
+        for (auto &kv : e->used) done = done && hipEventQuery(kv.second) == hipSuccess;
+        if (!done) continue;
+        std::shared_ptr<SpectrumRow> out = std::move(e);
+        r.spectrum_retired.erase(r.spectrum_retired.begin() + (long)i);
+        return out;
+    }
+    return nullptr;
+}
+
+int spectrum_row(int dev, hipStream_t s, const std::vector<uint64_t> &key,
+                 const std::function<int(float *)> &compute, std::shared_ptr<SpectrumRow> *out) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    DeviceRes &r = g_res[dev];
+    for (auto &e : r.spectrum)
+        if (e->key == key) {
+            // (the stream that computed the row too: a wait on an event of its own costs next to
+            // nothing, and a stream handle does not identify a stream once streams are destroyed)
+            DSPB_HIP(hipStreamWaitEvent(s, e->ready, 0));
+            *out = e;
+            return DSP_OK;
+        }
+    std::shared_ptr<SpectrumRow> e = spectrum_recycle(r);
+    if (!e) {
+        e = std::make_shared<SpectrumRow>();
+        DSPB_HIP(hipEventCreateWithFlags(&e->ready, hipEventDisableTiming));
+        if (hipError_t err = hipMalloc(&e->row, sizeof(float) * kSpectrumRowFloats)) {
+            (void)hipEventDestroy(e->ready);
+            return hip_fail(err, "hipMalloc");
+        }
+    }
+    e->key = key;
+    // with g_mu held, so that a second call of this key finds the event recorded
+    int st = compute(e->row);
+    if (st == DSP_OK && hipEventRecord(e->ready, s) != hipSuccess) st = DSP_ERR_HIP;
+    if (st) {  // the row serves a later miss
+        r.spectrum_retired.push_back(e);
+        return st;
+    }
+    if (r.spectrum.size() >= kSpectrumRows) {
+        r.spectrum_retired.push_back(std::move(r.spectrum.front()));
+        r.spectrum.erase(r.spectrum.begin());
+    }
+    r.spectrum.push_back(e);
+    *out = e;
+    return DSP_OK;
+}
+
+int spectrum_row_used(hipStream_t s, const std::shared_ptr<SpectrumRow> &e) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    hipEvent_t &ev = e->used[(void *)s];
+    if (!ev) DSPB_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    DSPB_HIP(hipEventRecord(ev, s));
+    return DSP_OK;
+}
+
+// ---------------------------------------------------------------------------
 // optional per-launch timing of the dominant kernel (HIP events on the
 // launch stream), read back by dsp_kernel_timing(); used by bench.py
 // ---------------------------------------------------------------------------
@@ -250,6 +316,8 @@ int timing_end(hipStream_t s, TimedLaunch *t, uint64_t bytes) {
 // DSP_DEBUG_FRAME_RUN (stft8192_pk_frame_run) and DSP_DEBUG_BIQUAD_SPIN_LIMIT
 // (capi_render.cpp iir_launch)
 std::atomic<uint32_t> g_frame_run{0}, g_iir_spin_limit{kIirSpinLimit};
+// DSP_DEBUG_SPECTRUM_CACHE and DSP_DEBUG_ROW_RUN (capi_render.cpp dsp_render_stft)
+std::atomic<uint32_t> g_spectrum_cache{0}, g_row_run{0};
 
 // ---------------------------------------------------------------------------
 // argument checks (before DeviceGuard: they need no device)
@@ -384,6 +452,16 @@ int dsp_debug_set(int what, uint64_t value) {
         g_frame_run.store((uint32_t)value);
         return DSP_OK;
     }
+    if (what == DSP_DEBUG_SPECTRUM_CACHE) {
+        if (value > 2) return invalid("dsp_debug_set: spectrum cache mode %llu > 2", (unsigned long long)value);
+        g_spectrum_cache.store((uint32_t)value);
+        return DSP_OK;
+    }
+    if (what == DSP_DEBUG_ROW_RUN) {
+        if (value > 0xffffu) return invalid("dsp_debug_set: row run %llu > 65535", (unsigned long long)value);
+        g_row_run.store((uint32_t)value);
+        return DSP_OK;
+    }
     if (what != DSP_DEBUG_BIQUAD_SPIN_LIMIT) return invalid("dsp_debug_set: unknown hook %d", what);
     g_iir_spin_limit.store(value > 0xffffffffull ? kIirSpinLimit : (uint32_t)value);
     return DSP_OK;
@@ -392,6 +470,10 @@ int dsp_debug_set(int what, uint64_t value) {
 int dsp_debug_get(int what, uint64_t *value) {
     if (what == DSP_DEBUG_FRAME_RUN && value) {
         *value = g_frame_run.load();
+        return DSP_OK;
+    }
+    if ((what == DSP_DEBUG_SPECTRUM_CACHE || what == DSP_DEBUG_ROW_RUN) && value) {
+        *value = (what == DSP_DEBUG_ROW_RUN ? g_row_run : g_spectrum_cache).load();
         return DSP_OK;
     }
     if (what != DSP_DEBUG_BIQUAD_REPAIRS || !value) return invalid("dsp_debug_get: unknown hook %d", what);

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <algorithm>
 #include <atomic>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -62,6 +63,21 @@ struct IirWork {
     uint64_t epoch = 0;
 };
 
+// One cached spectrum row of the fused IR_test STFT (spectrum_row): the 4097
+// magnitudes every frame of a call with H % B == 0 has, computed once per key
+// by the one-frame kernel.  The key is everything the row depends on.  A call
+// holds the entry (the shared_ptr) while it enqueues; an evicted entry is
+// retired, and its buffer serves a later miss once no call holds it and every
+// stream that read it has passed the event of its last use.
+struct SpectrumRow {
+    std::vector<uint64_t> key;
+    float *row = nullptr;              // kSpectrumRowFloats
+    hipEvent_t ready = nullptr;        // after the launch that computed the row, on that launch's stream
+    std::map<void *, hipEvent_t> used;  // per stream: after its last launch that read the row
+};
+constexpr size_t kSpectrumRowFloats = 4100;  // 4097 bins, whole 16-byte pieces
+constexpr size_t kSpectrumRows = 8;          // rows a device keeps
+
 struct DeviceRes {
     v2f *tw8192 = nullptr;  // exp(-2 pi i k / 8192), then 896 lane-major stage twiddles
     float4 *wbase = nullptr;  // (cos, sin)(theta 2l), (cos, sin)(theta (2l+1)), theta = 2 pi / 8191
@@ -73,6 +89,8 @@ struct DeviceRes {
     TableCache resample;                                       // dsp_resample conversions seen (up, down, spec)
     TableCache limiter;                                        // dsp_limiter tables seen (rho, lookahead)
     TableCache rfft;                                           // dsp_rfft twiddle tables seen (n)
+    std::vector<std::shared_ptr<SpectrumRow>> spectrum;        // fused IR_test spectrum rows seen, oldest first
+    std::vector<std::shared_ptr<SpectrumRow>> spectrum_retired;  // evicted: for the next misses
     std::map<void *, IirWork> iir_work;                        // per stream
     uint32_t *iir_fb_host = nullptr, *iir_fb_dev = nullptr;  // host-mapped counter of repaired launches
     float *delta = nullptr;  // 2048 floats: 1, 0, 0, ... (compute_IR's impulse, read-only)
@@ -191,8 +209,19 @@ enum ScratchSlot : int {
     kScratchLoudness = 3,    // a dsp_loudness channel group's partial sums, hop energies and peaks
     kScratchLimiter = 4,     // a dsp_limiter call's hold rows, tile aggregates, carries and result words
     kScratchBigFft = 5,      // a dsp_rfft / dsp_irfft / dsp_deconvolve channel group's work buffers and spectra
+    kScratchSpectrumHop = 6, // the hop the one-frame launch of a spectrum-row miss renders beside its row
 };
 int get_scratch(int dev, hipStream_t s, size_t bytes, float **out, ScratchSlot slot);
+
+// The cached spectrum row of `key` on `dev` for launches on s (not while s is
+// being captured).  A miss takes a retired row or allocates one, runs
+// compute(row) -- which enqueues on s the launch that fills it -- and records
+// the entry's ready event; a hit makes s wait for that event.  *out holds the
+// entry until spectrum_row_used(), which the caller calls after its launches
+// that read the row.
+int spectrum_row(int dev, hipStream_t s, const std::vector<uint64_t> &key,
+                 const std::function<int(float *)> &compute, std::shared_ptr<SpectrumRow> *out);
+int spectrum_row_used(hipStream_t s, const std::shared_ptr<SpectrumRow> &e);
 
 // ---------------------------------------------------------------------------
 // optional per-launch timing of the dominant kernel (capi.cpp)
@@ -213,6 +242,10 @@ int timing_end(hipStream_t s, TimedLaunch *t, uint64_t bytes);
 // BIQUAD look-back waits before it gives up
 constexpr uint32_t kIirSpinLimit = 1u << 16;
 extern std::atomic<uint32_t> g_frame_run, g_iir_spin_limit;
+// DSP_DEBUG_SPECTRUM_CACHE (0: the launch's own choice, 1: wherever it is
+// valid, 2: never) and DSP_DEBUG_ROW_RUN (frames per wave of the store-only
+// launch; 0: kRowRun)
+extern std::atomic<uint32_t> g_spectrum_cache, g_row_run;
 
 inline bool is_pow2(uint64_t n) { return n && !(n & (n - 1)); }
 inline uint32_t ilog2(uint64_t n) { uint32_t l = 0; while ((1ull << l) < n) ++l; return l; }

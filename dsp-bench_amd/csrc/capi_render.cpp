@@ -24,6 +24,43 @@ static int launch_stft(const Stft8kArgs &A, uint32_t C, bool fused, hipStream_t 
     return launch_stft8192_pk(A, C, fused, stft_pk_ab_options(), s);
 }
 
+// frames per wave of the store-only launch of a cached spectrum row
+// (stft8192_rows_kernel).  Measured at 1, 2 and 4 (profiles/r09_spectrum_cache_ab.txt):
+// with no FFT to share, the shortest run is the fastest -- 1 is 5% ahead of
+// the reuse launch, 2 level with it, 4 behind it
+constexpr uint32_t kRowRun = 1;
+
+// The device's cached spectrum row for the fused launch A (PER path, H % B ==
+// 0: every frame has the samples of frame 0) on s, not under capture.  The key
+// is what the row depends on: the block (a ramp's two parameters and whether
+// the kernel evaluates or loads it), B, the sample phase goff mod B, the
+// window's kind and pre-scaled coefficients, N and K.  A miss runs the
+// one-frame kernel on one frame of one channel -- its row is the cache's, its
+// hop goes to the stream's scratch -- so the row is what that kernel stores.
+static int cached_spectrum_row(const Stft8kArgs &A, int32_t window, int dev, hipStream_t s,
+                               std::shared_ptr<SpectrumRow> *row) {
+    auto bits = [](auto v) {
+        uint64_t u = 0;
+        std::memcpy(&u, &v, sizeof v);
+        return u;
+    };
+    const std::vector<uint64_t> key{A.map.closed, bits(A.map.rg0), bits(A.map.rs), A.map.B, A.goff % A.map.B,
+                                    (uint64_t)(uint32_t)window, bits(A.wa), bits(A.wb), 8192u, A.K};
+    float *hop = nullptr;
+    if (int st = get_scratch(dev, s, sizeof(float) * A.H, &hop, kScratchSpectrumHop)) return st;
+    return spectrum_row(dev, s, key, [&](float *dst) {
+        Stft8kArgs A1 = A;
+        A1.in_ch = 0;
+        A1.out.p[0] = hop;
+        A1.mag.p[0] = dst;
+        A1.F = 1;
+        A1.ld = A.K;
+        A1.tail_end = 0;
+        A1.run = 1;
+        return launch_stft8192_pk(A1, 1, true, 0, s);
+    }, row);
+}
+
 // ---------------------------------------------------------------------------
 // plugin -> sample map
 // ---------------------------------------------------------------------------
@@ -773,7 +810,7 @@ int dsp_render_stft(const float *const *in, uint32_t in_channels, uint64_t L,
         const float *win = nullptr;
         if ((st = get_tw(g.dev, s, &tw))) return st;
         if ((st = get_window(g.dev, s, window, N, N, &win, window_prescale(N)))) return st;
-        bool tail_in_kernel = false, reused = false;
+        bool tail_in_kernel = false, reused = false, cached = false;
         st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
             Stft8kArgs A{};
             fill_rows(din.data(), in_channels, dout.data(), c0, cn, &A.in, &A.in_ch, &A.out);
@@ -790,21 +827,45 @@ int dsp_render_stft(const float *const *in, uint32_t in_channels, uint64_t L,
             // rests on the class either
             const bool every_frame = ex && ((ex->flags & DSP_EXEC_EVERY_FRAME) ||
                                             (orig.kind == MapKind::Generic && (ex->flags & DSP_EXEC_VERIFY_CLASS)));
-            A.run = every_frame ? 1u : stft8192_pk_frame_run(A, true, cn, g_frame_run.load());
-            if (A.run > 1) reused = true;
+            const uint32_t forced_run = g_frame_run.load();
+            A.run = every_frame ? 1u : stft8192_pk_frame_run(A, true, cn, forced_run);
+            // ... and outside stream capture that one spectrum is the device's
+            // cached row of this block, phase and window (spectrum_row), which
+            // the launch only stores.  The row's key is the block's content:
+            // a ramp (closed form or IR_RAMP's own table) is its two
+            // parameters; a GENERIC plugin's table without a closed form has
+            // no content the host knows, and keeps the reuse launch.  Calls too
+            // short for frame reuse keep one frame per wave, and a forced
+            // DSP_DEBUG_FRAME_RUN keeps the reuse launch it asks for
+            const uint32_t mode = g_spectrum_cache.load();
+            const bool keyed = map.closed != 0 || orig.kind == MapKind::Ramp;
+            const bool row_path = !every_frame && !(ex && (ex->flags & DSP_EXEC_VERIFY_CLASS)) && mode != 2 && keyed &&
+                                  stft8192_pk_frame_run(A, true, cn, 2) == 2 &&  // (a forced run: wherever reuse is valid)
+                                  !capturing(s) &&
+                                  stft_pk_ab_options() == 0 &&  // (the tools build's variants are of the reuse launch)
+                                  (mode == 1 || (forced_run == 0 && A.run > 1));
+            std::shared_ptr<SpectrumRow> row;
+            if (row_path) {
+                if (int e = cached_spectrum_row(A, window, g.dev, s, &row)) return e;
+                A.run = g_row_run.load() ? g_row_run.load() : kRowRun;
+                cached = true;
+            }
+            if (A.run > 1 || row) reused = true;
             TimedLaunch tl{};
             if (int e = timing_begin(s, &tl)) return e;
-            if (int e = launch_stft(A, cn, true, s)) return e;
+            if (int e = row ? launch_stft8192_rows(A, cn, row->row, s) : launch_stft(A, cn, true, s)) return e;
             // algorithmic bytes: render write 4 B + magnitudes 4 K/H B
             // per hop sample, plus the file read when the map uses its input
             const uint64_t hop_samples = (uint64_t)cn * F * H;
             uint64_t bytes = hop_samples * 4 + (uint64_t)cn * F * K * 4;
             if (map.kind != MapKind::Ramp) bytes += (uint64_t)A.in_ch * F * H * 4;
             if (A.tail_end) bytes += (uint64_t)cn * (A.tail_end - F * (uint64_t)H) * 4;
-            return timing_end(s, &tl, bytes);
+            if (int e = timing_end(s, &tl, bytes)) return e;
+            return row ? spectrum_row_used(s, row) : (int)DSP_OK;
         });
         if (st) return st;
         if (reused) or_result(ex, DSP_RESULT_FRAME_REUSE);
+        if (cached) or_result(ex, DSP_RESULT_SPECTRUM_CACHE);
         // the render tail no frame owns: [F*H, Lr)
         if (!tail_in_kernel) {
             st = render_device(din.data(), in_channels, L, dout.data(), C, B, map, F * (uint64_t)H, goff, s);

@@ -276,6 +276,9 @@ bool stft8192_pk_per_path(const Stft8kArgs &A, bool fused);
 uint32_t stft8192_pk_frame_run(const Stft8kArgs &A, bool fused, uint32_t C, uint32_t forced);
 int stft_pk_ab_options();  // A/B option bits of this thread: 0 unless the tools build (stft_pk_ab.hip) set them
 int launch_stft8192_pk(const Stft8kArgs &A, uint32_t C, bool fused, int opt, hipStream_t s);
+// the PER path with H % B == 0 from a cached spectrum row (4097 magnitudes in
+// bin order): the hops and the rows of every frame, A.run frames per wave, no FFT
+int launch_stft8192_rows(const Stft8kArgs &A, uint32_t C, const float *row, hipStream_t s);
 int launch_fft_generic(const GenericFftArgs &A, uint64_t transforms, uint32_t C, hipStream_t s);
 int launch_gain(const float *in, float *out, float g, uint64_t n, hipStream_t s);
 int launch_set(float v, float *out, uint64_t n, hipStream_t s);

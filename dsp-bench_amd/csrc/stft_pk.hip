@@ -1,5 +1,6 @@
 // stft_pk.hip -- the 8192-point STFT dispatcher and the fused IR_test
-// kernels of the headline (PER path); the kernel is in stft_pk.hpp.
+// kernels of the headline (PER path, and the store-only launch of a cached
+// spectrum row); the kernels are in stft_pk.hpp.
 #include "stft_pk.hpp"
 
 namespace dspb {
@@ -120,6 +121,35 @@ int launch_stft8192_pk(const Stft8kArgs &A_, uint32_t C, bool fused, int opt, hi
         if (stft_pk_ab_dispatch(A, C, fused, opt, grid, stream, &st)) return st;
     }
     return launch_pk_paths(A, fused, km, pow2, winc, grid, stream);
+}
+
+// The store-only launch of a call whose spectrum row is cached (stft_pk.hpp
+// stft8192_rows_kernel; in this translation unit, so that a cold headline
+// call still loads one code object): A as for launch_stft8192_pk on the PER
+// path with H % B == 0, A.run frames per wave, `row` the call's 4097 cached
+// magnitudes.
+int launch_stft8192_rows(const Stft8kArgs &A_, uint32_t C, const float *row, hipStream_t stream) {
+    if (A_.F == 0 || C == 0) return DSP_OK;
+    Stft8kArgs A = A_;
+    if (!row || !stft8192_pk_per_path(A, true) || A.H % A.map.B != 0 || A.H % 128u != 0 || A.H > 8192u)
+        return DSP_ERR_INVALID;
+    if (A.run == 0) A.run = 1;
+    A.run_waves = (A.F + A.run - 1) / A.run;
+    const uint64_t tail = A.tail_end > A.F * A.H ? (A.tail_end - A.F * A.H + A.H - 1) / A.H : 0;
+    if (A.run_waves + tail > 0x7fffffffull) return DSP_ERR_INVALID;
+    const dim3 grid((uint32_t)(A.run_waves + tail), C);
+#define DSPB_PK_ROWS(p) hipLaunchKernelGGL((stft8192_rows_kernel<p>), grid, dim3(64), 0, stream, A, row)
+    switch (A.map.B <= 128u ? 1u : A.map.B / 128u) {  // the block table's period in 128 samples
+    case 1: DSPB_PK_ROWS(1); break;
+    case 2: DSPB_PK_ROWS(2); break;
+    case 4: DSPB_PK_ROWS(4); break;
+    case 8: DSPB_PK_ROWS(8); break;
+    case 16: DSPB_PK_ROWS(16); break;
+    default: return DSP_ERR_INVALID;
+    }
+#undef DSPB_PK_ROWS
+    DSPB_HIP(hipGetLastError());
+    return DSP_OK;
 }
 
 // The product library has no A/B variants: these weak definitions stand

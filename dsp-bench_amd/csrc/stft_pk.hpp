@@ -22,7 +22,8 @@
 // The kernel template lives in this header; its instantiations are split over
 // three translation units, so that each code object is loaded (on the first
 // launch of one of its kernels) only when its path is used: stft_pk.hip (the
-// dispatcher and the fused IR_test "PER" kernels of the headline),
+// dispatcher, the fused IR_test "PER" kernels of the headline and the
+// store-only stft8192_rows_kernel of a cached spectrum row),
 // stft_pk_paths.hip (the other fused maps and the memory-source STFT),
 // stft_pk_ab.hip (A/B and ablation options).
 #pragma once
@@ -367,6 +368,68 @@ __device__ __forceinline__ void per_render_hop(const Stft8kArgs &A, float *o, ui
     }
 }
 
+// the render tail no frame owns, [F H, tail_end): the H samples from fs on, one wave
+__device__ __forceinline__ void per_render_tail(const Stft8kArgs &A, uint32_t ch, uint64_t fs, uint32_t lane) {
+    if (fs < A.tail_end) {
+        const uint32_t p0 = (uint32_t)(A.goff + fs) + 2u * lane;
+        float *o = A.out.p[ch] + fs;
+        const uint64_t n = A.tail_end - fs;
+#pragma unroll 4
+        for (uint32_t b = 0; 128u * b < A.H; ++b) {
+            const uint32_t e = 128u * b + 2u * lane;  // even: tail_end is a multiple of B >= 2
+            if (e < n) {
+                const uint32_t q = (p0 + 128u * b) & A.map.b_mask;
+                const v2f t = A.map.closed ? v2f{ramp_value(A.map, q), ramp_value(A.map, q + 1)}
+                                           : v2f{A.map.table[q], A.map.table[q + 1]};
+                reinterpret_cast<v2f *>(o + 128u * b)[lane] = t;
+            }
+        }
+    }
+}
+
+// Frame reuse across calls (capi.cpp spectrum_row): the one spectrum of a call
+// whose frames are all the same (H % B == 0) comes from the per-device cache,
+// `row` = its 4097 magnitudes in bin order as the one-frame kernel stored them,
+// and the launch only stores.  One wave per workgroup; wave w owns the frames
+// [w run, w run + nrun) of its channel as in the reuse path of
+// stft8192_pk_kernel (same XCD remap, same tail waves): it gathers the table
+// pairs, issues the run's hops, loads the row into the register layout
+// split_y2<KEEP> leaves (M) and stores it nrun times with store_row_pieces --
+// the store instructions, cache policy and addresses of the reuse path.  No
+// window, no FFT, no twiddle loads.
+template <int PER>
+__global__ __launch_bounds__(64) void stft8192_rows_kernel(Stft8kArgs A, const float *__restrict__ row) {
+    __shared__ __attribute__((aligned(16))) float lds[64 * 65];  // store_row_pieces' tile
+    const uint32_t lane = threadIdx.x;
+    const uint32_t ch = blockIdx.y;
+    uint64_t f = xcd_remap(blockIdx.x, gridDim.x);
+    if (f >= A.run_waves) {  // a tail wave
+        f = A.F + (f - A.run_waves);
+        per_render_tail(A, ch, f * (uint64_t)A.H, lane);
+        return;
+    }
+    f *= A.run;
+    const uint64_t left = A.F - f;
+    const uint32_t nrun = left < A.run ? (uint32_t)left : A.run;
+    const uint64_t fs = f * (uint64_t)A.H;
+    cx2 X[PER >= 2 ? PER / 2 : 1];
+    per_gather<PER>(A, (uint32_t)(A.goff + fs) + 2u * lane, X);
+    float *o = A.out.p[ch] + fs;
+    for (uint32_t r = 0; r < nrun; ++r, o += A.H) per_render_hop<PER, !(kPkPerOpt & kPkRenderCached)>(A, o, lane, X);
+    float M[kPkRowRegs];  // store_row_y2's bins: lane + 64 q, 2048 + that, 4096 - that, 2048 - that
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        M[4 * q] = (row + lane)[64 * q];
+        M[4 * q + 1] = (row + 2048u + lane)[64 * q];
+        M[4 * q + 2] = (row + 4096u - lane)[-64 * q];
+        M[4 * q + 3] = (row + 2048u - lane)[-64 * q];
+    }
+    M[64] = row[1024];
+    M[65] = row[3072];
+    float *mrow = A.mag.p[ch] + f * A.ld;
+    for (uint32_t r = 0; r < nrun; ++r, mrow += A.ld) store_row_pieces<kPkRunRows == 2>(M, mrow, lane, lds);
+}
+
 template <int SRC, int KM, MapKind MK, bool POW2, bool WINC, int PER = 0, int OPT = kPkDefaultOpt, int OCC = 2>
 // (OCC waves per SIMD whatever the workgroup size: stated as waves per EU,
 // which __launch_bounds__' workgroup count does not pin for one-wave groups)
@@ -408,22 +471,7 @@ void stft8192_pk_kernel(Stft8kArgs A) {
     const uint64_t fs = f * (uint64_t)A.H;
     if (f >= A.F) {  // whole wave leaves; nothing below waits on other waves
         if constexpr (SOA) {
-            // the render tail no frame owns, [F H, tail_end): H samples per wave
-            if (fs < A.tail_end) {
-                const uint32_t p0 = (uint32_t)(A.goff + fs) + 2u * lane;
-                float *o = A.out.p[ch] + fs;
-                const uint64_t n = A.tail_end - fs;
-#pragma unroll 4
-                for (uint32_t b = 0; 128u * b < A.H; ++b) {
-                    const uint32_t e = 128u * b + 2u * lane;  // even: tail_end is a multiple of B >= 2
-                    if (e < n) {
-                        const uint32_t q = (p0 + 128u * b) & A.map.b_mask;
-                        const v2f t = A.map.closed ? v2f{ramp_value(A.map, q), ramp_value(A.map, q + 1)}
-                                                   : v2f{A.map.table[q], A.map.table[q + 1]};
-                        reinterpret_cast<v2f *>(o + 128u * b)[lane] = t;
-                    }
-                }
-            }
+            per_render_tail(A, ch, fs, lane);
         }
         return;
     }

@@ -133,8 +133,9 @@ typedef struct dsp_plugin {
                                       size (H % B == 0) every frame of the call holds the same
                                       samples, and a call long enough to fill the device computes
                                       the spectrum once per wave and stores it for a run of frames
-                                      (DSP_RESULT_FRAME_REUSE) -- the same bits, nothing kept between
-                                      calls.  A GENERIC call with DSP_EXEC_VERIFY_CLASS computes
+                                      (DSP_RESULT_FRAME_REUSE) -- the same bits.  Outside stream
+                                      capture that spectrum is kept per device between calls
+                                      (DSP_RESULT_SPECTRUM_CACHE).  A GENERIC call with DSP_EXEC_VERIFY_CLASS computes
                                       every frame too */
 /* the flags that choose how a call computes (not where its buffers live):
  * the chunked and sharded drivers pass them on to every chunk */
@@ -150,6 +151,12 @@ typedef struct dsp_plugin {
 #define DSP_RESULT_FRAME_REUSE 0x8u /* dsp_render_stft: the fused launch computed one spectrum per
                                       run of frames (see DSP_EXEC_EVERY_FRAME); the chunked and
                                       sharded drivers OR it across their chunks */
+#define DSP_RESULT_SPECTRUM_CACHE 0x10u /* dsp_render_stft, with DSP_RESULT_FRAME_REUSE: the one
+                                      spectrum of the call came from the device's cache of spectrum
+                                      rows (computed once per plugin block, window and block size,
+                                      then kept between calls) and the launch only stored it -- the
+                                      same bits.  Never under stream capture, DSP_EXEC_EVERY_FRAME
+                                      or DSP_EXEC_VERIFY_CLASS */
 
 typedef struct dsp_exec {
     int32_t device;         /* HIP device ordinal; -1 = current device */
@@ -482,8 +489,22 @@ int dsp_sweep_harmonic_offset(uint32_t sr, const dsp_sweep_spec *spec, uint32_t 
  * DSP_DEBUG_FRAME_RUN (set / get): frames per wave of the frame reuse (see
  *   DSP_EXEC_EVERY_FRAME) wherever it is valid, whatever the call's length
  *   (1..65535; 1 = every frame; 0 restores the launch's own choice).
- *   Process-wide: for tests and A/B runs. */
-enum { DSP_DEBUG_BIQUAD_SPIN_LIMIT = 1, DSP_DEBUG_BIQUAD_REPAIRS = 2, DSP_DEBUG_FRAME_RUN = 3 };
+ *   Process-wide: for tests and A/B runs.  A set value keeps the call on the
+ *   reuse launch: it then takes no cached spectrum row.
+ * DSP_DEBUG_SPECTRUM_CACHE (set / get): the cached spectrum row of the fused
+ *   IR_test launch (DSP_RESULT_SPECTRUM_CACHE).  0: the library's own choice
+ *   (calls long enough for frame reuse); 1: wherever the row is valid, whatever
+ *   the call's length; 2: never (every call takes the reuse launch).
+ * DSP_DEBUG_ROW_RUN (set / get): frames per wave of the store-only launch that
+ *   serves a cached row (1..65535; 0 restores the default).  Both process-wide:
+ *   for tests and A/B runs. */
+enum {
+    DSP_DEBUG_BIQUAD_SPIN_LIMIT = 1,
+    DSP_DEBUG_BIQUAD_REPAIRS = 2,
+    DSP_DEBUG_FRAME_RUN = 3,
+    DSP_DEBUG_SPECTRUM_CACHE = 4,
+    DSP_DEBUG_ROW_RUN = 5
+};
 int dsp_debug_set(int what, uint64_t value);
 int dsp_debug_get(int what, uint64_t *value);
 
