@@ -96,67 +96,25 @@
 //   RATE, default 48000, as BITS 16|24|32|float, default float; amplitude 0.5
 //   with 10 ms fades) as a mono WAV: the excitation of a measurement that
 //   --deconvolve evaluates.  Host only: no device is opened.
-#include <hip/hip_runtime.h>
-
+//
+// options.cpp reads the command line, device.hpp owns what lives on the device,
+// wavio.cpp is the one WAV loader and the one writer; here are the three modes.
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include <ctime>
-
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
-#include <vector>
+#include <ctime>
 
-#include "dspbench/dspbench.h"
-#include "dspbench/module.h"
 #include "dspbench/shard.h"
-#include "dspbench/wav.h"
+#include "options.hpp"
+#include "wavio.hpp"
 
 namespace {
 
-int fail(const char *what, int st) {
-    std::fprintf(stderr, "dspbench_render: %s: %s (%s)\n", what, dsp_status_string(st), dsp_last_error());
-    return 1;
-}
-
-#define HIPCK(x)                                                                          \
-    do {                                                                                  \
-        hipError_t e_ = (x);                                                              \
-        if (e_ != hipSuccess) {                                                           \
-            std::fprintf(stderr, "dspbench_render: %s: %s\n", #x, hipGetErrorString(e_)); \
-            return 1;                                                                     \
-        }                                                                                 \
-    } while (0)
-
-bool read_file(const char *path, std::vector<unsigned char> &out) {
-    FILE *f = std::fopen(path, "rb");
-    if (!f) return false;
-    std::fseek(f, 0, SEEK_END);
-    const long n = std::ftell(f);
-    std::fseek(f, 0, SEEK_SET);
-    out.resize(n > 0 ? (size_t)n : 0);
-    const bool ok = n >= 0 && std::fread(out.data(), 1, out.size(), f) == out.size();
-    std::fclose(f);
-    return ok;
-}
-
-void usage() {
-    std::fprintf(stderr,
-                 "usage: dspbench_render IN.wav OUT.wav [--plugin gain_test|IR_test|no_op|static_gain|PATH.cpp]\n"
-                 "       [--convolve IR.wav] [--gain G] [--ir G,STEP] [--block B] [--bits 16|24|32|float] [--stft MAG.f32]"
-                 " [--device N]\n"
-                 "       [--device-channels C] [--device-rate R] [--rate R] [--loop NBLOCKS]\n"
-                 "       [--loudness] [--normalize LUFS [--true-peak-ceiling DBTP [--limit]]]\n"
-                 "       [--limit-lookahead MS] [--limit-release MS]\n"
-                 "       [--deconvolve REF.wav [--deconv-eps E] [--deconv-pre N] [--ir-length N]]\n"
-                 "       [--world W --rank R --comm-id FILE [--run-id STR] [--chunk SAMPLES]]\n"
-                 "       dspbench_render --sweep F1:F2:SECONDS[:RATE[:BITS]] OUT.wav\n");
-}
+constexpr uint32_t N = 8192, H = 4096, K = N / 2 + 1;  // --stft: Hann 8192 / 4096
 
 // rank 0 writes the RCCL id and the run id to `path` (atomically: a temp
 // file renamed); the other ranks wait up to two minutes for a file carrying
@@ -202,653 +160,437 @@ std::string json_num(double v) {
     return b;
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-// --sweep SPEC OUT.wav (either order): the excitation as a mono WAV, host only
-int write_sweep(const char *spec_arg, const char *out_path) {
+// ---- --sweep: the excitation as a mono WAV, host only ------------------------
+int run_sweep(const Options &o) {
     dsp_sweep_spec sp{};
-    sp.amplitude = 0.5;
-    unsigned rate = 48000;
-    char bits_s[8] = "float", tail = 0;
-    const int got = std::sscanf(spec_arg, "%lf:%lf:%lf:%u:%7[a-z0-9]%c", &sp.f1, &sp.f2, &sp.seconds, &rate, bits_s, &tail);
-    const std::string bs = bits_s;
-    if (got < 3 || got > 5 || (bs != "float" && bs != "16" && bs != "24" && bs != "32")) {
-        usage();
-        return 2;
-    }
+    sp.amplitude = 0.5, sp.f1 = o.sweep_f1, sp.f2 = o.sweep_f2, sp.seconds = o.sweep_seconds;
+    const unsigned rate = o.sweep_rate;
     uint64_t L = 0;
-    sp.fade = 0;
     int st = dsp_sweep_plan(rate, &sp, &L, nullptr);
     if (st) return fail("dsp_sweep_plan", st);
     sp.fade = (uint32_t)std::min<uint64_t>(rate / 100, L / 2);  // 10 ms at each end
     std::vector<float> x(L);
     if ((st = dsp_sweep(rate, &sp, x.data(), L))) return fail("dsp_sweep", st);
-    const uint16_t fmt = bs == "float" ? DSP_WAV_FORMAT_FLOAT : DSP_WAV_FORMAT_PCM;
-    const uint16_t bits = bs == "float" ? 32 : (uint16_t)std::atoi(bits_s);
-    const size_t bps = bits / 8u;
-    std::vector<unsigned char> out(64 + L * bps);
-    const int hdr = dsp_wav_write_header(out.data(), out.size(), fmt, 1, rate, bits, L);
-    if (hdr < 0) return fail("dsp_wav_write_header", hdr);
+    const Format f = resolve_bits(o.sweep_bits, {});
+    const size_t bps = f.bits / 8u;
+    WavOut w;
+    if (int e = wav_header(w, f, 1, rate, L)) return e;
     for (uint64_t i = 0; i < L; ++i) {  // dsp_wav_encode's rounding, on the host
-        uint32_t w;
-        if (fmt == DSP_WAV_FORMAT_FLOAT) std::memcpy(&w, &x[i], 4);
-        else if (bits == 32) {
+        uint32_t code;
+        if (f.fmt == DSP_WAV_FORMAT_FLOAT) std::memcpy(&code, &x[i], 4);
+        else if (f.bits == 32) {
             const double r = std::min(std::max(std::rint((double)x[i] * 2147483648.0), -2147483648.0), 2147483647.0);
-            w = (uint32_t)(int32_t)r;
+            code = (uint32_t)(int32_t)r;
         } else {
-            const float S = bits == 16 ? 32768.f : 8388608.f;
-            w = (uint32_t)(int32_t)std::fmin(std::fmax(std::rint(x[i] * S), -S), S - 1.f);
+            const float S = f.bits == 16 ? 32768.f : 8388608.f;
+            code = (uint32_t)(int32_t)std::fmin(std::fmax(std::rint(x[i] * S), -S), S - 1.f);
         }
-        for (size_t b = 0; b < bps; ++b) out[hdr + i * bps + b] = (unsigned char)(w >> (8 * b));
+        for (size_t b = 0; b < bps; ++b) w.bytes[w.hdr + i * bps + b] = (unsigned char)(code >> (8 * b));
     }
-    FILE *f = std::fopen(out_path, "wb");
-    if (!f || std::fwrite(out.data(), 1, hdr + L * bps, f) != hdr + L * bps) {
-        std::fprintf(stderr, "dspbench_render: cannot write %s\n", out_path);
+    if (int e = write_file(o.out_path.c_str(), {{w.bytes.data(), w.size}})) return e;
+    std::printf("dspbench_render: sweep %g..%g Hz, %llu frames @ %u Hz -> %s (%s)\n", sp.f1, sp.f2,
+                (unsigned long long)L, rate, o.out_path.c_str(), o.sweep_bits.c_str());
+    return 0;
+}
+
+// the input file, for both device modes: refused before the device is opened
+int load_input(const Options &o, Device &dev, Wav &in) {
+    return load_wav(o.in_path.c_str(), "", [&](const dsp_wav_info &i) {
+        const uint32_t C = o.dev_channels ? o.dev_channels : i.channels;
+        if (i.channels == 0 || i.channels > 16 || C == 0 || C > 16) {
+            std::fprintf(stderr, "dspbench_render: %u file / %u device channels (1..16 supported)\n", i.channels, C);
+            return 1;
+        }
+        return 0;
+    }, dev, in);
+}
+
+// ---- --deconvolve: the recording deconvolved by REF's first channel ---------
+int run_deconvolve(const Options &o) {
+    Device dev(o.device);
+    Wav in, ref;
+    if (int e = load_input(o, dev, in)) return e;
+    const uint32_t Cf = in.info.channels, rate = in.info.sample_rate;
+    const uint64_t L = in.info.frames;
+    const char *ref_path = o.deconv_path.c_str();
+    if (int e = load_wav(ref_path, " (excitation)", [&](const dsp_wav_info &ri) {
+            if (ri.sample_rate != rate) {
+                std::fprintf(stderr, "dspbench_render: --deconvolve: %s is at %u Hz, %s at %u Hz\n", ref_path,
+                             ri.sample_rate, o.in_path.c_str(), rate);
+                return 1;
+            }
+            if (ri.frames == 0 || L == 0 || ri.channels == 0 || ri.channels > 16) {
+                std::fprintf(stderr, "dspbench_render: --deconvolve: an empty recording or excitation\n");
+                return 1;
+            }
+            return 0;
+        }, dev, ref))
+        return e;
+    uint32_t n = 0;
+    int st = dsp_deconv_plan(L, ref.info.frames, Cf, &n, nullptr);
+    if (st) return fail("dsp_deconv_plan", st);
+    const uint64_t irl = o.ir_length ? o.ir_length : std::min<uint64_t>(n, 1u << 20);
+    if (irl > n || o.deconv_pre > irl) {
+        std::fprintf(stderr, "dspbench_render: --deconvolve: needs --deconv-pre <= --ir-length <= n = %u\n", n);
+        return 2;
+    }
+    Rows ir;
+    HIPCK(ir.alloc(Cf, irl));
+    dsp_deconv_spec ds{};
+    ds.eps = o.deconv_eps;
+    ds.pre = (uint32_t)o.deconv_pre;
+    if ((st = dsp_deconvolve(in.rows.ptr.data(), Cf, L, ref.rows.ptr[0], ref.info.frames, ir.ptr.data(), irl, &ds, &dev.ex)))
+        return fail("dsp_deconvolve", st);
+    WavOut w;
+    if (int e = queue_wav(ir, Cf, irl, rate, resolve_bits(o.bits, {DSP_WAV_FORMAT_FLOAT, 32}), dev, w)) return e;
+    std::vector<float> h(irl);
+    std::string j = "{\"n\": " + std::to_string(n) + ", \"eps\": " + json_num(o.deconv_eps) + ", \"pre\": " +
+                    std::to_string(o.deconv_pre) + ", \"ir_length\": " + std::to_string(irl) + ", \"peaks\": [";
+    for (uint32_t c = 0; c < Cf; ++c) {  // each channel's peak
+        HIPCK(hipMemcpyAsync(h.data(), ir.ptr[c], irl * sizeof(float), hipMemcpyDeviceToHost, dev.stream.h));
+        HIPCK(hipStreamSynchronize(dev.stream.h));
+        uint64_t at = 0;
+        for (uint64_t i = 1; i < irl; ++i)
+            if (std::fabs(h[i]) > std::fabs(h[at])) at = i;
+        j += std::string(c ? ", " : "") + "{\"index\": " + std::to_string(at) + ", \"value\": " +
+             json_num((double)h[at]) + "}";
+    }
+    std::printf("%s]}\n", j.c_str());
+    if (int e = write_file(o.out_path.c_str(), {{w.bytes.data(), w.size}})) return e;
+    std::printf("dspbench_render: %s deconvolved by %s: %u ch x %llu frames @ %u Hz -> %s (n = %u), %.1f ms end to end\n",
+                o.in_path.c_str(), ref_path, Cf, (unsigned long long)irl, rate, o.out_path.c_str(), n, dev.ms());
+    return 0;
+}
+
+// ---- the render: what its stages hand on ------------------------------------
+struct Render {
+    const Options &o;
+    Device dev;
+    Wav in;
+    uint32_t Cf = 0, C = 0, Cin = 0, rate = 0;  // the file's channels, the device's, channels_to_write (audio.cpp:66)
+    uint64_t L = 0, nblocks = 0, Lr = 0, F = 0;  // input frames (--rate: converted), blocks, frames and STFT frames rendered
+    Rows out, mag;
+    dsp_plugin p{};
+    float pv[2] = {0.f, 0.f};
+    Module mod;
+    std::vector<unsigned char> gparams;
+    std::vector<float> taps;
+    Event e0, e1;
+    dsp_comm *comm = nullptr;
+    explicit Render(const Options &opt) : o(opt), dev(opt.device) {}
+};
+
+// --convolve: the IR file's first channel as the taps, at the render's rate
+int load_taps(Render &r) {
+    const Options &o = r.o;
+    const char *path = o.conv_path.c_str();
+    Wav ir;
+    if (int e = load_wav(path, " (impulse response)", [&](const dsp_wav_info &ii) {
+            if (ii.frames == 0 || ii.frames > (1u << 20) || ii.channels == 0 || ii.channels > 16) {
+                std::fprintf(stderr, "dspbench_render: %s: %llu frames, %u channels (1..2^20 frames, 1..16 channels)\n",
+                             path, (unsigned long long)ii.frames, ii.channels);
+                return 1;
+            }
+            return 0;
+        }, r.dev, ir))
+        return e;
+    uint64_t ntaps = ir.info.frames;
+    float tap_scale = 1.f;
+    if (o.rate && o.rate != ir.info.sample_rate) {  // --rate: the response at the render's rate, DC gain kept
+        if (int e = resample_rows(ir.rows, 1, ntaps, ir.info.sample_rate, o.rate, " (impulse response)", [&](uint64_t n) {
+                if (n == 0 || n > (1u << 20)) {
+                    std::fprintf(stderr, "dspbench_render: %s: %llu taps at %u Hz (1..2^20 supported)\n", path,
+                                 (unsigned long long)n, o.rate);
+                    return 1;
+                }
+                return 0;
+            }, r.dev))
+            return e;
+        tap_scale = (float)((double)ir.info.sample_rate / (double)o.rate);
+    }
+    r.taps.resize(ntaps);
+    HIPCK(hipMemcpyAsync(r.taps.data(), ir.rows.ptr[0], ntaps * sizeof(float), hipMemcpyDeviceToHost, r.dev.stream.h));
+    HIPCK(hipStreamSynchronize(r.dev.stream.h));
+    if (tap_scale != 1.f)
+        for (float &t : r.taps) t *= tap_scale;
+    return 0;
+}
+
+// a plugin source file: compile for gfx950, load, defaults, state
+int load_module(Render &r) {
+    const char *path = r.o.plugin.c_str();
+    std::vector<unsigned char> src;
+    if (!read_file(path, src)) {
+        std::fprintf(stderr, "dspbench_render: cannot read plugin %s\n", path);
         return 1;
     }
-    std::fclose(f);
-    std::printf("dspbench_render: sweep %g..%g Hz, %llu frames @ %u Hz -> %s (%s)\n", sp.f1, sp.f2,
-                (unsigned long long)L, rate, out_path, bits_s);
+    src.push_back(0);
+    void *code = nullptr;
+    uint64_t code_size = 0;
+    std::vector<char> log(1 << 16);
+    int st = dsp_module_compile((const char *)src.data(), path, &code, &code_size, log.data(), log.size());
+    if (st) {
+        std::fprintf(stderr, "%s\n", log.data());
+        return fail("dsp_module_compile", st);
+    }
+    st = dsp_module_load(code, code_size, r.dev.device, &r.mod.h);
+    dsp_module_free_code(code);
+    if (st) return fail("dsp_module_load", st);
+    uint32_t ps = 0, ss = 0;
+    int stateless = 0;
+    if ((st = dsp_module_sizes(r.mod.h, &ps, &ss, &stateless))) return fail("dsp_module_sizes", st);
+    r.gparams.resize(ps ? ps : 1);
+    if ((st = dsp_module_default_parameters(r.mod.h, r.gparams.data()))) return fail("dsp_module_default_parameters", st);
+    if ((st = dsp_module_initialize_state(r.mod.h, r.gparams.data(), r.C, (float)r.rate, 16u << 20)))
+        return fail("dsp_module_initialize_state", st);
+    r.p.kind = DSP_PLUGIN_GENERIC, r.p.params = r.gparams.data(), r.p.params_size = ps, r.p.module = r.mod.h;
+    return 0;
+}
+
+int make_plugin(Render &r) {
+    const Options &o = r.o;
+    dsp_plugin &p = r.p;
+    float *pv = r.pv;
+    if (!o.conv_path.empty()) {
+        if (int e = load_taps(r)) return e;
+        p.kind = DSP_PLUGIN_CONV, p.params = r.taps.data(), p.params_size = (uint32_t)(r.taps.size() * sizeof(float));
+    } else if (o.plugin == "gain_test") {
+        pv[0] = o.gain >= 0.f ? o.gain : 0.2f;  // build/gain_test.cpp:23
+        p.kind = DSP_PLUGIN_GAIN, p.params = pv, p.params_size = 4;
+    } else if (o.plugin == "static_gain") {
+        pv[0] = o.gain >= 0.f ? o.gain : 0.1f;  // test/static_gain_plugin.cpp:22
+        p.kind = DSP_PLUGIN_STATIC_GAIN, p.state = pv, p.state_size = 4;
+    } else if (o.plugin == "IR_test") {
+        pv[0] = o.ir_gain, pv[1] = o.ir_step;  // build/IR_test.cpp:24
+        p.kind = DSP_PLUGIN_IR_RAMP, p.params = pv, p.params_size = 8;
+    } else if (o.plugin == "no_op") {
+        p.kind = DSP_PLUGIN_NOOP;
+    } else {
+        return load_module(r);
+    }
+    return 0;
+}
+
+// cfg 5: this rank renders + STFTs its run of channels, rank 0 gathers every
+// channel (out / mag hold the whole file there)
+int render_sharded(Render &r) {
+    const Options &o = r.o;
+    const bool root = o.rank == 0;
+    dsp_shard sh{};
+    int st = dsp_shard_plan(r.L, r.C, o.world, o.rank, o.block, N, H, DSP_SHARD_CHANNELS, 1, &sh);
+    if (st) return fail("dsp_shard_plan", st);
+    Rows lown, lmag;  // this rank's run: renders (the root's are rows of r.out) and spectra
+    if (!root) HIPCK(lown.alloc(sh.channels, r.Lr));
+    HIPCK(lmag.alloc(sh.channels, (r.F ? r.F : 1) * K));
+    if (root) HIPCK(r.mag.alloc(r.C, (r.F ? r.F : 1) * K));
+    std::vector<float *> lout(sh.channels);
+    std::vector<const float *> lin;
+    for (uint32_t j = 0; j < sh.channels; ++j) {
+        const uint32_t c = sh.chan0 + j;
+        if (c < r.Cin) lin.push_back(r.in.rows.ptr[c]);
+        lout[j] = root ? r.out.ptr[c] : lown.ptr[j];
+    }
+    st = dsp_render_stft_sharded(lin.data(), (uint32_t)lin.size(), r.L, lout.data(), lmag.ptr.data(), K, r.C, o.block,
+                                 (float)r.rate, &r.p, N, H, DSP_WIN_HANN, K, &sh, o.chunk, r.comm, 0,
+                                 root ? r.out.ptr.data() : nullptr, root ? r.mag.ptr.data() : nullptr, &r.dev.ex);
+    if (st) return fail("dsp_render_stft_sharded", st);
+    HIPCK(hipStreamSynchronize(r.dev.stream.h));
+    return 0;
+}
+
+// the render (+ STFT) between the two events, as one of sharded / loop / stft / offline
+int render(Render &r, time_t started) {
+    const Options &o = r.o;
+    const float sr = (float)r.rate;
+    const uint32_t B = o.block;
+    float *const *in = r.in.rows.ptr.data(), *const *out = r.out.ptr.data();
+    hipStream_t s = r.dev.stream.h;
+    r.F = o.stft_path.empty() ? 0 : dsp_stft_frame_count(r.Lr, N, H);
+    HIPCK(hipEventCreate(&r.e0.h));
+    HIPCK(hipEventCreate(&r.e1.h));
+    int st = 0;
+    if (o.multi()) {
+        unsigned char id[DSP_COMM_ID_BYTES];
+        if (!exchange_comm_id(o.comm_path, o.rank, o.run_id, started, id)) {
+            std::fprintf(stderr, "dspbench_render: rank %u: no communicator id at %s\n", o.rank, o.comm_path.c_str());
+            return 1;
+        }
+        if ((st = dsp_comm_init(id, o.world, o.rank, r.dev.device, &r.comm))) return fail("dsp_comm_init", st);
+        // every rank has joined (the init is collective): the id is spent
+        if (o.rank == 0) (void)std::remove(o.comm_path.c_str());
+    }
+    HIPCK(hipEventRecord(r.e0.h, s));
+    if (o.multi()) {
+        if (int e = render_sharded(r)) return e;
+    } else if (o.loop_blocks) {
+        uint64_t cursor = 0;
+        if ((st = dsp_render_loop(in, r.Cin, r.L, 0, out, r.C, B, r.nblocks, sr, &r.p, &cursor, &r.dev.ex)))
+            return fail("dsp_render_loop", st);
+    } else if (r.F > 0) {
+        HIPCK(r.mag.alloc(r.C, r.F * K));
+        st = dsp_render_stft(in, r.Cin, r.L, out, r.C, B, sr, &r.p, N, H, DSP_WIN_HANN, K, r.mag.ptr.data(), K, &r.dev.ex);
+        if (st) return fail("dsp_render_stft", st);
+    } else {
+        if ((st = dsp_render_offline(in, r.Cin, r.L, out, r.C, B, sr, &r.p, &r.dev.ex))) return fail("dsp_render_offline", st);
+    }
+    HIPCK(hipEventRecord(r.e1.h, s));
+    return 0;
+}
+
+std::string loudness_json(const Options &o, const dsp_loudness_result &lr, float g, const dsp_limiter_result &lim,
+                          float residual) {
+    std::string j = "{\"integrated\": " + json_num(lr.integrated) + ", \"range\": " + json_num(lr.range) +
+                    ", \"momentary_max\": " + json_num(lr.momentary_max) + ", \"short_term_max\": " +
+                    json_num(lr.short_term_max) + ", \"sample_peak\": " + json_num(lr.sample_peak) +
+                    ", \"true_peak\": " + json_num(lr.true_peak) + ", \"blocks\": " + std::to_string(lr.blocks) +
+                    ", \"gated_blocks\": " + std::to_string(lr.gated_blocks);
+    if (o.normalize) j += ", \"gain\": " + json_num((double)g);
+    if (o.limit)
+        j += ", \"limiter\": {\"min_gain\": " + json_num(lim.min_gain) + ", \"limited\": " + std::to_string(lim.limited) +
+             ", \"residual_gain\": " + json_num((double)residual) + "}";
+    return j + "}";
+}
+
+// --loudness / --normalize: the loudness of the render, and the gain to a target level
+int level(Render &r) {
+    const Options &o = r.o;
+    float *const *out = r.out.ptr.data();
+    auto measure = [&](dsp_loudness_result &lr) {
+        return dsp_loudness(out, r.C, r.Lr, r.rate, nullptr, DSP_LOUDNESS_TRUE_PEAK, nullptr, nullptr, nullptr, &lr, &r.dev.ex);
+    };
+    // the largest gain <= g0 that keeps `peak` at or below the ceiling
+    auto fit = [&](double peak, float g0) {
+        const double limit = std::pow(10.0, o.ceiling_dbtp / 20.0);
+        if (peak * (double)g0 > limit) {
+            g0 = (float)(limit / peak);
+            while (g0 > 0.f && peak * (double)g0 > limit) g0 = std::nextafterf(g0, 0.f);
+        }
+        return g0;
+    };
+    auto scale = [&](float by) {
+        for (uint32_t c = 0; c < r.C; ++c)
+            if (int e = dsp_gain(out[c], out[c], by, r.Lr, &r.dev.ex)) return e;
+        return 0;
+    };
+    dsp_loudness_result lr{};
+    int st = measure(lr);
+    if (st) return fail("dsp_loudness", st);
+    float g = 1.f, residual = 1.f;
+    dsp_limiter_result lim{};
+    if (o.normalize) {
+        if (!std::isfinite(lr.integrated)) {
+            std::fprintf(stderr, "dspbench_render: --normalize: the render's integrated loudness is %s "
+                                 "(no block passes the gates)\n", json_num(lr.integrated).c_str());
+            return 1;
+        }
+        g = (float)std::pow(10.0, (o.norm_lufs - lr.integrated) / 20.0);
+        if (o.ceiling && !o.limit) g = fit(lr.true_peak, g);
+        if ((st = scale(g))) return fail("dsp_gain", st);
+    }
+    if (o.normalize && o.limit) {
+        // the level stays: the limiter turns down the peaks, then a scalar gain takes what is
+        // left of the true peak above the ceiling (the limiter's gain moves between samples)
+        dsp_limiter_spec ls{};
+        ls.ceiling = (float)std::pow(10.0, o.ceiling_dbtp / 20.0);
+        const double la = std::floor(o.limit_lookahead_ms * 1e-3 * (double)r.rate + 0.5);
+        ls.lookahead = (uint32_t)(la < 1024.0 ? la : 1024.0);
+        ls.release = o.limit_release_ms * 1e-3 * (double)r.rate;
+        if (ls.release > 0.0 && ls.release < 1.0) ls.release = 1.0;
+        ls.flags = DSP_LIMITER_TRUE_PEAK;
+        if ((st = dsp_limiter(out, r.C, r.Lr, out, r.rate, &ls, nullptr, nullptr, nullptr, &lim, &r.dev.ex)))
+            return fail("dsp_limiter", st);
+        dsp_loudness_result after{};
+        if ((st = measure(after))) return fail("dsp_loudness", st);
+        residual = fit(after.true_peak, 1.f);
+        if (residual != 1.f && (st = scale(residual))) return fail("dsp_gain", st);
+    }
+    if (o.loudness || o.limit) std::printf("%s\n", loudness_json(o, lr, g, lim, residual).c_str());
+    return 0;
+}
+
+// encode the render and write it, with the spectra (header "DSPMAG1\0", u32 C, u32 K, u64 F)
+int write_outputs(Render &r) {
+    const Options &o = r.o;
+    const uint64_t F = r.F;
+    hipStream_t s = r.dev.stream.h;
+    const Format f = resolve_bits(o.bits, {r.in.info.format, r.in.info.bits_per_sample});
+    WavOut w;
+    if (int e = queue_wav(r.out, r.C, r.Lr, r.rate, f, r.dev, w)) return e;
+    std::vector<float> mag((size_t)r.C * F * K);
+    float *const *dmag = r.mag.ptr.data();
+    for (uint32_t c = 0; F > 0 && c < r.C; ++c)
+        HIPCK(hipMemcpyAsync(mag.data() + (size_t)c * F * K, dmag[c], F * K * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    float render_ms = 0.f;
+    HIPCK(hipEventElapsedTime(&render_ms, r.e0.h, r.e1.h));
+    if (int e = write_file(o.out_path.c_str(), {{w.bytes.data(), w.size}})) return e;
+    const uint32_t ck[2] = {r.C, K};
+    if (F > 0)
+        if (int e = write_file(o.stft_path.c_str(), {{"DSPMAG1", 8}, {ck, 8}, {&F, 8}, {mag.data(), mag.size() * 4}}))
+            return e;
+    std::printf("dspbench_render: %s: %u ch x %llu frames @ %u Hz -> %s (%s %u-bit, %llu blocks of %u)%s; "
+                "render %.3f ms on the GPU, %.1f ms end to end\n",
+                o.in_path.c_str(), r.C, (unsigned long long)r.L, r.rate, o.out_path.c_str(),
+                f.fmt == DSP_WAV_FORMAT_FLOAT ? "float" : "PCM", f.bits, (unsigned long long)r.nblocks, o.block,
+                F ? (" + STFT " + std::to_string(F) + " frames x " + std::to_string(K) + " bins").c_str() : "",
+                render_ms, r.dev.ms());
+    return 0;
+}
+
+// a rank other than 0 of the multi-GPU mode: only the root writes
+int finish_rank(Render &r) {
+    HIPCK(hipStreamSynchronize(r.dev.stream.h));
+    float ms = 0.f;
+    HIPCK(hipEventElapsedTime(&ms, r.e0.h, r.e1.h));
+    std::printf("dspbench_render: rank %u of %u: channels rendered and gathered to rank 0 in %.3f ms\n", r.o.rank,
+                r.o.world, ms);
+    dsp_comm_destroy(r.comm);
+    return 0;
+}
+
+// ---- the render modes: load, plugin, render, level, write -------------------
+int run_render(const Options &o, time_t started) {
+    Render r(o);
+    if (int e = load_input(o, r.dev, r.in)) return e;
+    const dsp_wav_info &info = r.in.info;
+    r.Cf = info.channels;
+    r.C = o.dev_channels ? o.dev_channels : r.Cf;
+    r.Cin = std::min(r.Cf, r.C);
+    r.rate = o.rate ? o.rate : o.dev_rate ? o.dev_rate : info.sample_rate;
+    r.L = info.frames;
+    if (o.rate && o.rate != info.sample_rate)  // --rate: the file at the new rate replaces the decoded one
+        if (int e = resample_rows(r.in.rows, r.Cf, r.L, info.sample_rate, o.rate, "", [](uint64_t) { return 0; }, r.dev))
+            return e;
+    r.nblocks = o.loop_blocks ? o.loop_blocks : (r.L + o.block - 1) / o.block;
+    r.Lr = r.nblocks * o.block;
+    HIPCK(r.out.alloc(r.C, r.Lr));
+    r.mag.ptr.assign(r.C, nullptr);  // (--loop computes no spectra: with --stft their copy fails, as it always has)
+    if (int e = make_plugin(r)) return e;
+    if (int e = render(r, started)) return e;
+    if (o.multi() && o.rank != 0) return finish_rank(r);
+    if (o.loudness || o.normalize)
+        if (int e = level(r)) return e;
+    if (int e = write_outputs(r)) return e;
+    if (r.comm) dsp_comm_destroy(r.comm);
     return 0;
 }
 
 }  // namespace
 
 int main(int argc, char **argv) {
-    for (int i = 1; i < argc; ++i)
-        if (std::string(argv[i]) == "--sweep") {  // its value and one positional argument, nothing else
-            if (argc != 4 || i > 2) {
-                usage();
-                return 2;
-            }
-            return write_sweep(argv[i + 1], argv[i == 1 ? 3 : 1]);
-        }
-    if (argc < 3) {
-        usage();
-        return 2;
-    }
-    const char *in_path = argv[1], *out_path = argv[2];
-    std::string plugin = "gain_test", stft_path, bits_opt, conv_path, deconv_path;
-    double deconv_eps = 1e-6;
-    uint64_t deconv_pre = 0, ir_length = 0;
-    bool have_plugin = false;
-    float gain = -1.f, ir_gain = 0.9f, ir_step = 0.002f;
-    uint32_t B = 512;
-    int device = -1;
-    uint32_t dev_channels = 0, dev_rate = 0, conv_rate = 0, world = 0, rank = 0;
-    uint64_t loop_blocks = 0, chunk = 16ull << 20;
-    bool have_rank = false;
-    bool want_loudness = false, want_normalize = false, want_ceiling = false;
-    bool want_limit = false;
-    double norm_lufs = 0.0, ceiling_dbtp = 0.0, limit_lookahead_ms = 1.5, limit_release_ms = 100.0;
-    std::string comm_path, run_id;
     const time_t started = std::time(nullptr) - 2;  // (mtime has one-second resolution)
-    if (const char *e = std::getenv("DSPB_RUN_ID")) run_id = e;
-    else if (const char *e2 = std::getenv("TORCHELASTIC_RUN_ID")) run_id = e2;
-    for (int i = 3; i < argc; i += 2) {  // every option but --loudness and --limit takes one value
-        const std::string a = argv[i];
-        if (a == "--loudness" || a == "--limit") {
-            (a == "--limit" ? want_limit : want_loudness) = true;
-            --i;
-            continue;
-        }
-        const char *v = i + 1 < argc ? argv[i + 1] : nullptr;
-        if (!v) {
-            usage();
-            return 2;
-        }
-        if (a == "--plugin") plugin = v, have_plugin = true;
-        else if (a == "--convolve") conv_path = v;
-        else if (a == "--deconvolve") deconv_path = v;
-        else if (a == "--deconv-eps") deconv_eps = std::strtod(v, nullptr);
-        else if (a == "--deconv-pre") deconv_pre = std::strtoull(v, nullptr, 10);
-        else if (a == "--ir-length") {
-            ir_length = std::strtoull(v, nullptr, 10);
-            if (ir_length == 0) {
-                usage();
-                return 2;
-            }
-        }
-        else if (a == "--gain") gain = std::strtof(v, nullptr);
-        else if (a == "--ir") {
-            if (std::sscanf(v, "%f,%f", &ir_gain, &ir_step) != 2) {
-                usage();
-                return 2;
-            }
-        } else if (a == "--block") B = (uint32_t)std::strtoul(v, nullptr, 10);
-        else if (a == "--bits") bits_opt = v;
-        else if (a == "--stft") stft_path = v;
-        else if (a == "--device") device = std::atoi(v);
-        else if (a == "--device-channels") dev_channels = (uint32_t)std::strtoul(v, nullptr, 10);
-        else if (a == "--device-rate") dev_rate = (uint32_t)std::strtoul(v, nullptr, 10);
-        else if (a == "--rate") {
-            conv_rate = (uint32_t)std::strtoul(v, nullptr, 10);
-            if (conv_rate == 0) {
-                usage();
-                return 2;
-            }
-        } else if (a == "--normalize" || a == "--true-peak-ceiling" || a == "--limit-lookahead" ||
-                   a == "--limit-release") {
-            char *end = nullptr;
-            const double val = std::strtod(v, &end);
-            if (end == v || *end) {  // not a number
-                usage();
-                return 2;
-            }
-            if (a == "--normalize") norm_lufs = val, want_normalize = true;
-            else if (a == "--true-peak-ceiling") ceiling_dbtp = val, want_ceiling = true;
-            else if (a == "--limit-lookahead") limit_lookahead_ms = val;
-            else limit_release_ms = val;
-        }
-        else if (a == "--loop") loop_blocks = std::strtoull(v, nullptr, 10);
-        else if (a == "--world") world = (uint32_t)std::strtoul(v, nullptr, 10);
-        else if (a == "--rank") rank = (uint32_t)std::strtoul(v, nullptr, 10), have_rank = true;
-        else if (a == "--comm-id") comm_path = v;
-        else if (a == "--run-id") run_id = v;
-        else if (a == "--chunk") chunk = std::strtoull(v, nullptr, 10);
-        else {
-            usage();
-            return 2;
-        }
+    Env env;
+    env.dspb_run_id = std::getenv("DSPB_RUN_ID"), env.torchelastic_run_id = std::getenv("TORCHELASTIC_RUN_ID");
+    env.world_size = std::getenv("WORLD_SIZE"), env.rank = std::getenv("RANK"), env.local_rank = std::getenv("LOCAL_RANK");
+    const Parsed p = parse_options(argc, argv, env);
+    if (p.status) {
+        if (p.message) std::fputs(p.message, stderr);
+        if (p.usage) std::fputs(usage_text(), stderr);
+        return p.status;
     }
-    if (B == 0) {
-        usage();
-        return 2;
+    switch (p.opt.mode) {
+    case Options::SWEEP: return run_sweep(p.opt);
+    case Options::DECONVOLVE: return run_deconvolve(p.opt);
+    default: return run_render(p.opt, started);
     }
-    if (have_plugin && !conv_path.empty()) {
-        std::fprintf(stderr, "dspbench_render: --convolve and --plugin exclude each other\n");
-        return 2;
-    }
-    const bool multi = !comm_path.empty();
-    if (!deconv_path.empty() && (have_plugin || !conv_path.empty() || loop_blocks || multi || world || conv_rate ||
-                                 !stft_path.empty() || want_loudness || want_normalize || want_ceiling || want_limit)) {
-        std::fprintf(stderr, "dspbench_render: --deconvolve excludes --plugin, --convolve, --loop, --stft, --rate, "
-                             "--loudness, --normalize and the multi-GPU modes\n");
-        usage();
-        return 2;
-    }
-    if (deconv_path.empty() && (deconv_pre || ir_length || deconv_eps != 1e-6)) {
-        std::fprintf(stderr, "dspbench_render: --deconv-eps, --deconv-pre and --ir-length need --deconvolve\n");
-        usage();
-        return 2;
-    }
-    if (conv_rate && (dev_rate || loop_blocks || multi || world)) {
-        std::fprintf(stderr, "dspbench_render: --rate excludes --device-rate, --loop and the multi-GPU modes\n");
-        usage();
-        return 2;
-    }
-    if ((want_loudness || want_normalize || want_ceiling || want_limit) && (loop_blocks || multi || world)) {
-        std::fprintf(stderr, "dspbench_render: --loudness, --normalize, --true-peak-ceiling and --limit exclude --loop "
-                             "and the multi-GPU modes\n");
-        usage();
-        return 2;
-    }
-    if (want_ceiling && !want_normalize) {
-        std::fprintf(stderr, "dspbench_render: --true-peak-ceiling needs --normalize\n");
-        usage();
-        return 2;
-    }
-    if (want_limit && !(want_normalize && want_ceiling)) {
-        std::fprintf(stderr, "dspbench_render: --limit needs --normalize and --true-peak-ceiling\n");
-        usage();
-        return 2;
-    }
-    if (want_limit && !(limit_lookahead_ms >= 0.0 && limit_release_ms >= 0.0)) {
-        usage();
-        return 2;
-    }
-    if ((want_normalize && !std::isfinite(norm_lufs)) || (want_ceiling && !std::isfinite(ceiling_dbtp))) {
-        usage();
-        return 2;
-    }
-    if (multi) {  // torchrun-style environment when not given explicitly
-        const char *ew = std::getenv("WORLD_SIZE"), *er = std::getenv("RANK");
-        if (!world) world = ew ? (uint32_t)std::atoi(ew) : 1;
-        if (!have_rank) rank = er ? (uint32_t)std::atoi(er) : 0;
-        if (device < 0) {
-            const char *lr = std::getenv("LOCAL_RANK");
-            device = lr ? std::atoi(lr) : (int)rank;
-        }
-        if (world == 0 || rank >= world || stft_path.empty() || loop_blocks) {
-            std::fprintf(stderr, "dspbench_render: --comm-id needs --stft, rank < world and no --loop\n");
-            return 2;
-        }
-    }
-    if (device < 0) device = 0;
-
-    // ---- load + parse (wav_reader.h:57-205) --------------------------------
-    std::vector<unsigned char> file;
-    if (!read_file(in_path, file)) {
-        std::fprintf(stderr, "dspbench_render: cannot read %s\n", in_path);
-        return 1;
-    }
-    dsp_wav_info info{};
-    int st = dsp_wav_parse(file.data(), file.size(), &info);
-    if (st) return fail("dsp_wav_parse", st);
-    const uint32_t Cf = info.channels;                // the file's channels
-    const uint32_t C = dev_channels ? dev_channels : Cf;  // the device's (the render's)
-    const uint32_t Cin = Cf < C ? Cf : C;             // channels_to_write (audio.cpp:66)
-    const uint32_t rate = conv_rate ? conv_rate : dev_rate ? dev_rate : info.sample_rate;
-    uint64_t L = info.frames;  // (--rate: the converted length from the conversion on)
-    if (Cf == 0 || Cf > 16 || C == 0 || C > 16) {
-        std::fprintf(stderr, "dspbench_render: %u file / %u device channels (1..16 supported)\n", Cf, C);
-        return 1;
-    }
-    std::vector<unsigned char> payload(info.data_bytes);
-    for (uint64_t c = 0, o = 0; c < info.n_data_chunks; ++c) {  // the data chunks, concatenated
-        std::memcpy(payload.data() + o, file.data() + info.data_offset[c], info.data_size[c]);
-        o += info.data_size[c];
-    }
-    file.clear();
-    file.shrink_to_fit();
-
-    HIPCK(hipSetDevice(device));
-    hipStream_t s;
-    HIPCK(hipStreamCreate(&s));
-    dsp_exec ex{};
-    ex.device = device;
-    ex.stream = s;
-
-    // ---- payload -> HBM, decode to planar float (audio.h:66-121) ----------
-    const auto t0 = std::chrono::steady_clock::now();
-    void *d_pay = nullptr;
-    HIPCK(hipMalloc(&d_pay, payload.size() + 16));
-    HIPCK(hipMemcpyAsync(d_pay, payload.data(), payload.size(), hipMemcpyHostToDevice, s));
-    std::vector<float *> din(Cf), dout(C);
-    for (uint32_t c = 0; c < Cf; ++c) HIPCK(hipMalloc(&din[c], (L ? L : 1) * sizeof(float)));
-    if ((st = dsp_wav_decode(d_pay, &info, 0, L, din.data(), &ex))) return fail("dsp_wav_decode", st);
-    if (conv_rate && conv_rate != info.sample_rate) {  // --rate: the file at the new rate replaces the decoded one
-        uint64_t Ln = 0;
-        if ((st = dsp_resample_plan(info.sample_rate, conv_rate, L, nullptr, nullptr, nullptr, nullptr, &Ln, nullptr)))
-            return fail("dsp_resample_plan", st);
-        std::vector<float *> dnew(Cf);
-        for (uint32_t c = 0; c < Cf; ++c) HIPCK(hipMalloc(&dnew[c], (Ln ? Ln : 1) * sizeof(float)));
-        if ((st = dsp_resample(din.data(), Cf, L, dnew.data(), Ln, info.sample_rate, conv_rate, nullptr, &ex)))
-            return fail("dsp_resample", st);
-        HIPCK(hipStreamSynchronize(s));
-        for (uint32_t c = 0; c < Cf; ++c) {
-            HIPCK(hipFree(din[c]));
-            din[c] = dnew[c];
-        }
-        L = Ln;
-    }
-    if (!deconv_path.empty()) {
-        // ---- swept-sine measurement: the recording deconvolved by REF's first channel ----
-        std::vector<unsigned char> rf;
-        if (!read_file(deconv_path.c_str(), rf)) {
-            std::fprintf(stderr, "dspbench_render: cannot read %s\n", deconv_path.c_str());
-            return 1;
-        }
-        dsp_wav_info ri{};
-        if ((st = dsp_wav_parse(rf.data(), rf.size(), &ri))) return fail("dsp_wav_parse (excitation)", st);
-        if (ri.sample_rate != info.sample_rate) {
-            std::fprintf(stderr, "dspbench_render: --deconvolve: %s is at %u Hz, %s at %u Hz\n", deconv_path.c_str(),
-                         ri.sample_rate, in_path, info.sample_rate);
-            return 1;
-        }
-        if (ri.frames == 0 || L == 0 || ri.channels == 0 || ri.channels > 16) {
-            std::fprintf(stderr, "dspbench_render: --deconvolve: an empty recording or excitation\n");
-            return 1;
-        }
-        std::vector<unsigned char> rp(ri.data_bytes);
-        for (uint64_t c = 0, o = 0; c < ri.n_data_chunks; ++c) {
-            std::memcpy(rp.data() + o, rf.data() + ri.data_offset[c], ri.data_size[c]);
-            o += ri.data_size[c];
-        }
-        void *d_ref = nullptr;
-        HIPCK(hipMalloc(&d_ref, rp.size() + 16));
-        HIPCK(hipMemcpyAsync(d_ref, rp.data(), rp.size(), hipMemcpyHostToDevice, s));
-        std::vector<float *> dref(ri.channels);
-        for (uint32_t c = 0; c < ri.channels; ++c) HIPCK(hipMalloc(&dref[c], ri.frames * sizeof(float)));
-        if ((st = dsp_wav_decode(d_ref, &ri, 0, ri.frames, dref.data(), &ex))) return fail("dsp_wav_decode", st);
-        uint32_t n = 0;
-        if ((st = dsp_deconv_plan(L, ri.frames, Cf, &n, nullptr))) return fail("dsp_deconv_plan", st);
-        const uint64_t irl = ir_length ? ir_length : std::min<uint64_t>(n, 1u << 20);
-        if (irl > n || deconv_pre > irl) {
-            std::fprintf(stderr, "dspbench_render: --deconvolve: needs --deconv-pre <= --ir-length <= n = %u\n", n);
-            return 2;
-        }
-        std::vector<float *> dir(Cf);
-        for (uint32_t c = 0; c < Cf; ++c) HIPCK(hipMalloc(&dir[c], irl * sizeof(float)));
-        dsp_deconv_spec ds{};
-        ds.eps = deconv_eps;
-        ds.pre = (uint32_t)deconv_pre;
-        if ((st = dsp_deconvolve(din.data(), Cf, L, dref[0], ri.frames, dir.data(), irl, &ds, &ex)))
-            return fail("dsp_deconvolve", st);
-        uint16_t fmt = DSP_WAV_FORMAT_FLOAT, bits = 32;
-        if (!bits_opt.empty() && bits_opt != "float") fmt = DSP_WAV_FORMAT_PCM, bits = (uint16_t)std::atoi(bits_opt.c_str());
-        const uint64_t out_bytes = irl * Cf * (bits / 8u);
-        void *d_opay = nullptr;
-        HIPCK(hipMalloc(&d_opay, out_bytes + 16));
-        if ((st = dsp_wav_encode(dir.data(), Cf, irl, fmt, bits, d_opay, &ex))) return fail("dsp_wav_encode", st);
-        std::vector<unsigned char> out(64 + out_bytes);
-        const int hdr = dsp_wav_write_header(out.data(), out.size(), fmt, (uint16_t)Cf, info.sample_rate, bits, irl);
-        if (hdr < 0) return fail("dsp_wav_write_header", hdr);
-        HIPCK(hipMemcpyAsync(out.data() + hdr, d_opay, out_bytes, hipMemcpyDeviceToHost, s));
-        std::vector<float> h(irl);
-        std::string j = "{\"n\": " + std::to_string(n) + ", \"eps\": " + json_num(deconv_eps) + ", \"pre\": " +
-                        std::to_string(deconv_pre) + ", \"ir_length\": " + std::to_string(irl) + ", \"peaks\": [";
-        for (uint32_t c = 0; c < Cf; ++c) {  // each channel's peak
-            HIPCK(hipMemcpyAsync(h.data(), dir[c], irl * sizeof(float), hipMemcpyDeviceToHost, s));
-            HIPCK(hipStreamSynchronize(s));
-            uint64_t at = 0;
-            for (uint64_t i = 1; i < irl; ++i)
-                if (std::fabs(h[i]) > std::fabs(h[at])) at = i;
-            j += std::string(c ? ", " : "") + "{\"index\": " + std::to_string(at) + ", \"value\": " +
-                 json_num((double)h[at]) + "}";
-        }
-        std::printf("%s]}\n", j.c_str());
-        FILE *f = std::fopen(out_path, "wb");
-        if (!f || std::fwrite(out.data(), 1, hdr + out_bytes, f) != hdr + out_bytes) {
-            std::fprintf(stderr, "dspbench_render: cannot write %s\n", out_path);
-            return 1;
-        }
-        std::fclose(f);
-        std::printf("dspbench_render: %s deconvolved by %s: %u ch x %llu frames @ %u Hz -> %s (n = %u), %.1f ms end to end\n",
-                    in_path, deconv_path.c_str(), Cf, (unsigned long long)irl, info.sample_rate, out_path, n, ms_since(t0));
-        for (float *q : dir) (void)hipFree(q);
-        for (float *q : dref) (void)hipFree(q);
-        for (float *q : din) (void)hipFree(q);
-        (void)hipFree(d_ref);
-        (void)hipFree(d_opay);
-        (void)hipFree(d_pay);
-        (void)hipStreamDestroy(s);
-        return 0;
-    }
-    const uint64_t nblocks = loop_blocks ? loop_blocks : (L + B - 1) / B, Lr = nblocks * B;
-    for (uint32_t c = 0; c < C; ++c) HIPCK(hipMalloc(&dout[c], Lr * sizeof(float)));
-
-    // ---- plugin ------------------------------------------------------------
-    dsp_plugin p{};
-    float pv[2] = {0.f, 0.f};
-    dsp_module *mod = nullptr;
-    std::vector<unsigned char> gparams;
-    std::vector<float> taps;
-    if (!conv_path.empty()) {  // the IR file's first channel, through the same parse + GPU decode
-        std::vector<unsigned char> irf;
-        if (!read_file(conv_path.c_str(), irf)) {
-            std::fprintf(stderr, "dspbench_render: cannot read %s\n", conv_path.c_str());
-            return 1;
-        }
-        dsp_wav_info ii{};
-        if ((st = dsp_wav_parse(irf.data(), irf.size(), &ii))) return fail("dsp_wav_parse (impulse response)", st);
-        if (ii.frames == 0 || ii.frames > (1u << 20) || ii.channels == 0 || ii.channels > 16) {
-            std::fprintf(stderr, "dspbench_render: %s: %llu frames, %u channels (1..2^20 frames, 1..16 channels)\n",
-                         conv_path.c_str(), (unsigned long long)ii.frames, ii.channels);
-            return 1;
-        }
-        std::vector<unsigned char> irp(ii.data_bytes);
-        for (uint64_t c = 0, o = 0; c < ii.n_data_chunks; ++c) {
-            std::memcpy(irp.data() + o, irf.data() + ii.data_offset[c], ii.data_size[c]);
-            o += ii.data_size[c];
-        }
-        void *d_ir = nullptr;
-        HIPCK(hipMalloc(&d_ir, irp.size() + 16));
-        HIPCK(hipMemcpyAsync(d_ir, irp.data(), irp.size(), hipMemcpyHostToDevice, s));
-        std::vector<float *> dir(ii.channels);
-        for (uint32_t c = 0; c < ii.channels; ++c) HIPCK(hipMalloc(&dir[c], ii.frames * sizeof(float)));
-        if ((st = dsp_wav_decode(d_ir, &ii, 0, ii.frames, dir.data(), &ex))) return fail("dsp_wav_decode", st);
-        uint64_t ntaps = ii.frames;
-        float tap_scale = 1.f;
-        if (conv_rate && conv_rate != ii.sample_rate) {  // --rate: the response at the render's rate, DC gain kept
-            if ((st = dsp_resample_plan(ii.sample_rate, conv_rate, ii.frames, nullptr, nullptr, nullptr, nullptr, &ntaps,
-                                        nullptr)))
-                return fail("dsp_resample_plan (impulse response)", st);
-            if (ntaps == 0 || ntaps > (1u << 20)) {
-                std::fprintf(stderr, "dspbench_render: %s: %llu taps at %u Hz (1..2^20 supported)\n", conv_path.c_str(),
-                             (unsigned long long)ntaps, conv_rate);
-                return 1;
-            }
-            float *dres = nullptr;
-            HIPCK(hipMalloc(&dres, ntaps * sizeof(float)));
-            if ((st = dsp_resample(dir.data(), 1, ii.frames, &dres, ntaps, ii.sample_rate, conv_rate, nullptr, &ex)))
-                return fail("dsp_resample (impulse response)", st);
-            HIPCK(hipStreamSynchronize(s));
-            HIPCK(hipFree(dir[0]));
-            dir[0] = dres;
-            tap_scale = (float)((double)ii.sample_rate / (double)conv_rate);
-        }
-        taps.resize(ntaps);
-        HIPCK(hipMemcpyAsync(taps.data(), dir[0], ntaps * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIPCK(hipStreamSynchronize(s));
-        if (tap_scale != 1.f)
-            for (float &t : taps) t *= tap_scale;
-        for (float *q : dir) HIPCK(hipFree(q));
-        HIPCK(hipFree(d_ir));
-        p.kind = DSP_PLUGIN_CONV, p.params = taps.data(), p.params_size = (uint32_t)(taps.size() * sizeof(float));
-    } else if (plugin == "gain_test") {
-        pv[0] = gain >= 0.f ? gain : 0.2f;  // build/gain_test.cpp:23
-        p.kind = DSP_PLUGIN_GAIN, p.params = pv, p.params_size = 4;
-    } else if (plugin == "static_gain") {
-        pv[0] = gain >= 0.f ? gain : 0.1f;  // test/static_gain_plugin.cpp:22
-        p.kind = DSP_PLUGIN_STATIC_GAIN, p.state = pv, p.state_size = 4;
-    } else if (plugin == "IR_test") {
-        pv[0] = ir_gain, pv[1] = ir_step;  // build/IR_test.cpp:24
-        p.kind = DSP_PLUGIN_IR_RAMP, p.params = pv, p.params_size = 8;
-    } else if (plugin == "no_op") {
-        p.kind = DSP_PLUGIN_NOOP;
-    } else {  // a plugin source file: compile for gfx950, load, defaults, state
-        std::vector<unsigned char> src;
-        if (!read_file(plugin.c_str(), src)) {
-            std::fprintf(stderr, "dspbench_render: cannot read plugin %s\n", plugin.c_str());
-            return 1;
-        }
-        src.push_back(0);
-        void *code = nullptr;
-        uint64_t code_size = 0;
-        std::vector<char> log(1 << 16);
-        if ((st = dsp_module_compile((const char *)src.data(), plugin.c_str(), &code, &code_size, log.data(),
-                                     log.size()))) {
-            std::fprintf(stderr, "%s\n", log.data());
-            return fail("dsp_module_compile", st);
-        }
-        st = dsp_module_load(code, code_size, device, &mod);
-        dsp_module_free_code(code);
-        if (st) return fail("dsp_module_load", st);
-        uint32_t ps = 0, ss = 0;
-        int stateless = 0;
-        if ((st = dsp_module_sizes(mod, &ps, &ss, &stateless))) return fail("dsp_module_sizes", st);
-        gparams.resize(ps ? ps : 1);
-        if ((st = dsp_module_default_parameters(mod, gparams.data()))) return fail("dsp_module_default_parameters", st);
-        if ((st = dsp_module_initialize_state(mod, gparams.data(), C, (float)rate, 16u << 20)))
-            return fail("dsp_module_initialize_state", st);
-        p.kind = DSP_PLUGIN_GENERIC, p.params = gparams.data(), p.params_size = ps, p.module = mod;
-    }
-
-    // ---- render (+ STFT) ---------------------------------------------------
-    const float sr = (float)rate;
-    const uint32_t N = 8192, H = 4096, K = N / 2 + 1;
-    const uint64_t F = stft_path.empty() ? 0 : dsp_stft_frame_count(Lr, N, H);
-    std::vector<float *> dmag(C, nullptr);
-    hipEvent_t e0, e1;
-    HIPCK(hipEventCreate(&e0));
-    HIPCK(hipEventCreate(&e1));
-    dsp_comm *comm = nullptr;
-    if (multi) {
-        unsigned char id[DSP_COMM_ID_BYTES];
-        if (!exchange_comm_id(comm_path, rank, run_id, started, id)) {
-            std::fprintf(stderr, "dspbench_render: rank %u: no communicator id at %s\n", rank, comm_path.c_str());
-            return 1;
-        }
-        if ((st = dsp_comm_init(id, world, rank, device, &comm))) return fail("dsp_comm_init", st);
-        // every rank has joined (the init is collective): the id is spent
-        if (rank == 0) (void)std::remove(comm_path.c_str());
-    }
-    HIPCK(hipEventRecord(e0, s));
-    if (multi) {
-        // cfg 5: this rank renders + STFTs its run of channels, rank 0
-        // gathers every channel (dout / dmag hold the whole file there)
-        dsp_shard sh{};
-        if ((st = dsp_shard_plan(L, C, world, rank, B, N, H, DSP_SHARD_CHANNELS, 1, &sh)))
-            return fail("dsp_shard_plan", st);
-        std::vector<float *> lout(sh.channels), lmag(sh.channels);
-        std::vector<const float *> lin;
-        for (uint32_t j = 0; j < sh.channels; ++j) {
-            const uint32_t c = sh.chan0 + j;
-            if (c < Cin) lin.push_back(din[c]);
-            if (rank == 0) {
-                lout[j] = dout[c];
-            } else {
-                HIPCK(hipMalloc(&lout[j], Lr * sizeof(float)));
-            }
-            HIPCK(hipMalloc(&lmag[j], (F ? F : 1) * K * sizeof(float)));
-        }
-        if (rank == 0)
-            for (uint32_t c = 0; c < C; ++c) HIPCK(hipMalloc(&dmag[c], (F ? F : 1) * K * sizeof(float)));
-        st = dsp_render_stft_sharded(lin.data(), (uint32_t)lin.size(), L, lout.data(), lmag.data(), K, C, B, sr, &p,
-                                     N, H, DSP_WIN_HANN, K, &sh, chunk, comm, 0, rank == 0 ? dout.data() : nullptr,
-                                     rank == 0 ? dmag.data() : nullptr, &ex);
-        if (st) return fail("dsp_render_stft_sharded", st);
-        HIPCK(hipStreamSynchronize(s));
-        for (uint32_t j = 0; j < sh.channels; ++j) {
-            if (rank != 0) (void)hipFree(lout[j]);
-            (void)hipFree(lmag[j]);
-        }
-    } else if (loop_blocks) {
-        uint64_t cursor = 0;
-        if ((st = dsp_render_loop(din.data(), Cin, L, 0, dout.data(), C, B, nblocks, sr, &p, &cursor, &ex)))
-            return fail("dsp_render_loop", st);
-    } else if (!stft_path.empty() && F > 0) {
-        for (uint32_t c = 0; c < C; ++c) HIPCK(hipMalloc(&dmag[c], F * K * sizeof(float)));
-        st = dsp_render_stft(din.data(), Cin, L, dout.data(), C, B, sr, &p, N, H, DSP_WIN_HANN, K, dmag.data(), K,
-                             &ex);
-        if (st) return fail("dsp_render_stft", st);
-    } else {
-        if ((st = dsp_render_offline(din.data(), Cin, L, dout.data(), C, B, sr, &p, &ex)))
-            return fail("dsp_render_offline", st);
-    }
-    HIPCK(hipEventRecord(e1, s));
-    if (multi && rank != 0) {  // only the root writes
-        HIPCK(hipStreamSynchronize(s));
-        float ms = 0.f;
-        HIPCK(hipEventElapsedTime(&ms, e0, e1));
-        std::printf("dspbench_render: rank %u of %u: channels rendered and gathered to rank 0 in %.3f ms\n", rank,
-                    world, ms);
-        dsp_comm_destroy(comm);
-        return 0;
-    }
-
-    // ---- loudness of the render, and the gain to a target level ------------
-    if (want_loudness || want_normalize) {
-        dsp_loudness_result lr{};
-        if ((st = dsp_loudness(dout.data(), C, Lr, rate, nullptr, DSP_LOUDNESS_TRUE_PEAK, nullptr, nullptr, nullptr, &lr,
-                               &ex)))
-            return fail("dsp_loudness", st);
-        float g = 1.f, residual = 1.f;
-        dsp_limiter_result lim{};
-        if (want_normalize) {
-            if (!std::isfinite(lr.integrated)) {
-                std::fprintf(stderr, "dspbench_render: --normalize: the render's integrated loudness is %s "
-                                     "(no block passes the gates)\n", json_num(lr.integrated).c_str());
-                return 1;
-            }
-            g = (float)std::pow(10.0, (norm_lufs - lr.integrated) / 20.0);
-            // the largest gain <= g0 that keeps `peak` at or below the ceiling
-            auto fit = [&](double peak, float g0) {
-                const double limit = std::pow(10.0, ceiling_dbtp / 20.0);
-                if (peak * (double)g0 > limit) {
-                    g0 = (float)(limit / peak);
-                    while (g0 > 0.f && peak * (double)g0 > limit) g0 = std::nextafterf(g0, 0.f);
-                }
-                return g0;
-            };
-            auto scale = [&](float by) {
-                for (uint32_t c = 0; c < C; ++c)
-                    if (int e = dsp_gain(dout[c], dout[c], by, Lr, &ex)) return e;
-                return 0;
-            };
-            if (want_ceiling && !want_limit) g = fit(lr.true_peak, g);
-            if ((st = scale(g))) return fail("dsp_gain", st);
-            if (want_limit) {
-                // the level stays: the limiter turns down the peaks, then a scalar gain takes what is
-                // left of the true peak above the ceiling (the limiter's gain moves between samples)
-                dsp_limiter_spec ls{};
-                ls.ceiling = (float)std::pow(10.0, ceiling_dbtp / 20.0);
-                const double la = std::floor(limit_lookahead_ms * 1e-3 * (double)rate + 0.5);
-                ls.lookahead = (uint32_t)(la < 1024.0 ? la : 1024.0);
-                ls.release = limit_release_ms * 1e-3 * (double)rate;
-                if (ls.release > 0.0 && ls.release < 1.0) ls.release = 1.0;
-                ls.flags = DSP_LIMITER_TRUE_PEAK;
-                if ((st = dsp_limiter(dout.data(), C, Lr, dout.data(), rate, &ls, nullptr, nullptr, nullptr, &lim, &ex)))
-                    return fail("dsp_limiter", st);
-                dsp_loudness_result after{};
-                if ((st = dsp_loudness(dout.data(), C, Lr, rate, nullptr, DSP_LOUDNESS_TRUE_PEAK, nullptr, nullptr,
-                                       nullptr, &after, &ex)))
-                    return fail("dsp_loudness", st);
-                residual = fit(after.true_peak, 1.f);
-                if (residual != 1.f && (st = scale(residual))) return fail("dsp_gain", st);
-            }
-        }
-        if (want_loudness || want_limit) {
-            std::string j = "{\"integrated\": " + json_num(lr.integrated) + ", \"range\": " + json_num(lr.range) +
-                            ", \"momentary_max\": " + json_num(lr.momentary_max) + ", \"short_term_max\": " +
-                            json_num(lr.short_term_max) + ", \"sample_peak\": " + json_num(lr.sample_peak) +
-                            ", \"true_peak\": " + json_num(lr.true_peak) + ", \"blocks\": " +
-                            std::to_string(lr.blocks) + ", \"gated_blocks\": " + std::to_string(lr.gated_blocks);
-            if (want_normalize) j += ", \"gain\": " + json_num((double)g);
-            if (want_limit)
-                j += ", \"limiter\": {\"min_gain\": " + json_num(lim.min_gain) + ", \"limited\": " +
-                     std::to_string(lim.limited) + ", \"residual_gain\": " + json_num((double)residual) + "}";
-            std::printf("%s}\n", j.c_str());
-        }
-    }
-
-    // ---- encode the render (audio.h:123-133 interleave) and write ----------
-    uint16_t fmt = info.format, bits = info.bits_per_sample;
-    if (bits_opt == "float") fmt = DSP_WAV_FORMAT_FLOAT, bits = 32;
-    else if (!bits_opt.empty()) fmt = DSP_WAV_FORMAT_PCM, bits = (uint16_t)std::atoi(bits_opt.c_str());
-    const uint64_t out_bytes = Lr * C * (bits / 8u);
-    void *d_opay = nullptr;
-    HIPCK(hipMalloc(&d_opay, out_bytes + 16));
-    if ((st = dsp_wav_encode(dout.data(), C, Lr, fmt, bits, d_opay, &ex))) return fail("dsp_wav_encode", st);
-    std::vector<unsigned char> out(64 + out_bytes);
-    const int hdr = dsp_wav_write_header(out.data(), out.size(), fmt, (uint16_t)C, rate, bits, Lr);
-    if (hdr < 0) return fail("dsp_wav_write_header", hdr);
-    HIPCK(hipMemcpyAsync(out.data() + hdr, d_opay, out_bytes, hipMemcpyDeviceToHost, s));
-    std::vector<float> mag;
-    if (F > 0) {
-        mag.resize((size_t)C * F * K);
-        for (uint32_t c = 0; c < C; ++c)
-            HIPCK(hipMemcpyAsync(mag.data() + (size_t)c * F * K, dmag[c], F * K * sizeof(float),
-                                 hipMemcpyDeviceToHost, s));
-    }
-    HIPCK(hipStreamSynchronize(s));
-    float render_ms = 0.f;
-    HIPCK(hipEventElapsedTime(&render_ms, e0, e1));
-    FILE *f = std::fopen(out_path, "wb");
-    if (!f || std::fwrite(out.data(), 1, hdr + out_bytes, f) != hdr + out_bytes) {
-        std::fprintf(stderr, "dspbench_render: cannot write %s\n", out_path);
-        return 1;
-    }
-    std::fclose(f);
-    if (F > 0) {
-        f = std::fopen(stft_path.c_str(), "wb");
-        const uint32_t hk[2] = {C, K};
-        if (!f || std::fwrite("DSPMAG1", 1, 8, f) != 8 || std::fwrite(hk, 4, 2, f) != 2 ||
-            std::fwrite(&F, 8, 1, f) != 1 || std::fwrite(mag.data(), 4, mag.size(), f) != mag.size()) {
-            std::fprintf(stderr, "dspbench_render: cannot write %s\n", stft_path.c_str());
-            return 1;
-        }
-        std::fclose(f);
-    }
-    std::printf("dspbench_render: %s: %u ch x %llu frames @ %u Hz -> %s (%s %u-bit, %llu blocks of %u)%s; "
-                "render %.3f ms on the GPU, %.1f ms end to end\n",
-                in_path, C, (unsigned long long)L, rate, out_path,
-                fmt == DSP_WAV_FORMAT_FLOAT ? "float" : "PCM", bits, (unsigned long long)nblocks, B,
-                F ? (" + STFT " + std::to_string(F) + " frames x " + std::to_string(K) + " bins").c_str() : "",
-                render_ms, ms_since(t0));
-
-    if (mod) dsp_module_destroy(mod);
-    if (comm) dsp_comm_destroy(comm);
-    for (uint32_t c = 0; c < Cf; ++c) (void)hipFree(din[c]);
-    for (uint32_t c = 0; c < C; ++c) {
-        (void)hipFree(dout[c]);
-        if (dmag[c]) (void)hipFree(dmag[c]);
-    }
-    (void)hipFree(d_pay);
-    (void)hipFree(d_opay);
-    (void)hipStreamDestroy(s);
-    return 0;
 }

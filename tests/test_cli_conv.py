@@ -3,28 +3,17 @@ The IR file goes through the same parse + GPU decode as the input, its first
 channel is the taps; the written file equals the Python face's render of the
 decoded input with those taps bit for bit.  --convolve with --plugin is a
 usage error (exit 2, no GPU touched)."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import dspbench as d
-from wavutil import wav_image
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "dsp-bench_amd", "dspbench_render")
+from cliutil import pcm16_file, run, split_chunks
 
 pytestmark = pytest.mark.gpu
 
 
-def run(*args):
-    return subprocess.run([CLI, *args], capture_output=True, text=True, timeout=300)
-
-
-def _pcm16(path, channels, L, seed):
-    raw = np.random.default_rng(seed).integers(-32768, 32768, size=channels * L, dtype=np.int64).astype("<i2")
-    path.write_bytes(wav_image(raw.tobytes(), fmt=1, channels=channels, bits=16))
+def _pcm16(path, channels, L, seed, **image):
+    pcm16_file(path, channels, L, seed, **image)
     return path
 
 
@@ -52,3 +41,19 @@ def test_convolve_file_matches_python_render(torch_cuda, tmp_path):
     want = want.cpu().numpy()
     got = np.asarray(got)
     assert got.shape == want.shape and np.array_equal(got, want)
+
+
+def test_response_split_over_two_data_chunks(torch_cuda, tmp_path):
+    """--convolve reads its file through the input's loader: a 257-tap response
+    in two data chunks, an odd-sized unrelated chunk between them, gives the
+    bytes of the same taps in one chunk."""
+    src = _pcm16(tmp_path / "in.wav", 2, 3001, 23)
+    one = _pcm16(tmp_path / "ir_one.wav", 1, 257, 24)
+    two = _pcm16(tmp_path / "ir_two.wav", 1, 257, 24, **split_chunks(2 * 257, 2 * 100))
+    assert len(two.read_bytes()) == len(one.read_bytes()) + 8 + 8 + 6
+    outs = []
+    for ir in (one, two):
+        outs.append(tmp_path / ("out_" + ir.name))
+        r = run(str(src), str(outs[-1]), "--convolve", str(ir), "--block", "256", "--bits", "float")
+        assert r.returncode == 0, r.stderr
+    assert outs[0].read_bytes() == outs[1].read_bytes() and len(outs[0].read_bytes()) == 46 + 12 * 256 * 8

@@ -5,22 +5,16 @@ SWEEP.wav gives the known band-limited response back within the float64
 model's recorded margin (deconvutil.RECOVERY_TOL) plus the device's DEC_TOL."""
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import dspbench as d
 import deconvutil as du
+from cliutil import run, split_chunks
 from wavutil import wav_image
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "dsp-bench_amd", "dspbench_render")
 S = du.SWEEP  # what `--sweep 50:20000:0.5` writes: amplitude 0.5, 10 ms fades, 48 kHz
-
-
-def run(*args, env=None):
-    return subprocess.run([CLI, *args], capture_output=True, text=True, timeout=300, env=env)
 
 
 def float_wav(path, x, sr=48000):
@@ -128,3 +122,27 @@ def test_sweep_convolve_deconvolve_recovers_the_response(torch_cuda, tmp_path):
     assert read_wav(got)[0].shape == (2, 32768)
     r = run(str(played), str(tmp_path / "again.wav"), "--convolve", str(got), "--bits", "float")
     assert r.returncode == 0, r.stderr
+
+
+@pytest.mark.gpu
+def test_excitation_split_over_two_data_chunks(torch_cuda, tmp_path):
+    """--deconvolve reads its file through the input's loader: a 0.05 s sweep in
+    two data chunks, an odd-sized unrelated chunk between them, gives the bytes
+    (and the JSON line) of the same sweep in one chunk."""
+    sweep = tmp_path / "sweep.wav"
+    assert run("--sweep", "50:20000:0.05", str(sweep)).returncode == 0
+    x = read_wav(sweep)[0]
+    assert x.shape == (1, 2400)
+    data = x[0].astype("<f4").tobytes()
+    one, two = tmp_path / "ref_one.wav", tmp_path / "ref_two.wav"
+    one.write_bytes(wav_image(data, fmt=3, channels=1, bits=32))
+    two.write_bytes(wav_image(data, fmt=3, channels=1, bits=32, **split_chunks(len(data), 4 * 1001)))
+    assert len(two.read_bytes()) == len(one.read_bytes()) + 8 + 8 + 6
+    outs, lines = [], []
+    for ref in (one, two):
+        outs.append(tmp_path / ("ir_" + ref.name))
+        r = run(str(sweep), str(outs[-1]), "--deconvolve", str(ref))
+        assert r.returncode == 0, r.stderr
+        lines.append([ln for ln in r.stdout.splitlines() if ln.startswith("{")])
+    assert outs[0].read_bytes() == outs[1].read_bytes() and lines[0] == lines[1] and len(lines[0]) == 1
+    assert read_wav(outs[0])[0].shape[0] == 1

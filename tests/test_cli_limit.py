@@ -9,24 +9,17 @@ The file: 2 s of a -20 dBFS 1 kHz tone in stereo with three bursts of 1 ms at
 with --limit -16.18 LUFS (the bursts' own energy and the release after them
 are what is lost), without it -21.85 LUFS; a residual gain of 1 - 3e-8."""
 import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import dspbench as d
+from cliutil import run
 from wavutil import wav_image
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "dsp-bench_amd", "dspbench_render")
 SR = 48000
 
 pytestmark = pytest.mark.gpu
-
-
-def run(*args):
-    return subprocess.run([CLI, *args], capture_output=True, text=True, timeout=300)
 
 
 def tone_with_bursts(path):

@@ -3,45 +3,25 @@ render is measured with dsp_loudness (its written frames, every channel at
 weight 1, true peak on), the result printed as one JSON line, and the render
 scaled to the target level by one fp32 gain before the encode.  Without the
 flags the output is byte for byte what it was."""
-import json
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import dspbench as d
-from wavutil import wav_image
+from cliutil import cuda as _cuda, json_line as _json_line, pcm16_file, run
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "dsp-bench_amd", "dspbench_render")
 FIELDS = ("integrated", "range", "momentary_max", "short_term_max", "sample_peak", "true_peak")
 
 pytestmark = pytest.mark.gpu
 
 
-def run(*args):
-    return subprocess.run([CLI, *args], capture_output=True, text=True, timeout=300)
-
-
 def _pcm16(path, L=48_000, seed=51, amp=8000, spike=None, silent=False):
-    raw = np.random.default_rng(seed).integers(-amp, amp + 1, size=2 * L, dtype=np.int64).astype("<i2")
-    if silent:
-        raw[:] = 0
-    if spike is not None:
-        raw[2 * spike] = 32700          # one near-full-scale sample on the left channel
-    path.write_bytes(wav_image(raw.tobytes(), fmt=1, channels=2, bits=16, sr=48000))
+    def edit(raw):
+        if silent:
+            raw[:] = 0
+        if spike is not None:
+            raw[2 * spike] = 32700      # one near-full-scale sample on the left channel
+    pcm16_file(path, 2, L, seed, lo=-amp, hi=amp + 1, edit=edit)
     return path
-
-
-def _cuda(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a))).cuda()
-
-
-def _json_line(stdout):
-    lines = [ln for ln in stdout.splitlines() if ln.startswith("{")]
-    assert len(lines) == 1, stdout
-    return json.loads(lines[0])
 
 
 def _measure(torch, path):

@@ -3,33 +3,18 @@ on the GPU before the render (dsp_resample, default quality), R goes to the
 plugin and into the output header; with --convolve the impulse response is
 converted from its own rate and scaled by ir_rate / R.  Without --rate the
 output is byte for byte what it was."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import dspbench as d
-from wavutil import wav_image
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "dsp-bench_amd", "dspbench_render")
+from cliutil import cuda as _cuda, pcm16_file, run
 
 pytestmark = pytest.mark.gpu
 
 
-def run(*args):
-    return subprocess.run([CLI, *args], capture_output=True, text=True, timeout=300)
-
-
 def _pcm16(path, channels, L, seed, rate):
-    raw = np.random.default_rng(seed).integers(-32768, 32768, size=channels * L, dtype=np.int64).astype("<i2")
-    path.write_bytes(wav_image(raw.tobytes(), fmt=1, channels=channels, bits=16, sr=rate))
+    pcm16_file(path, channels, L, seed, sr=rate)
     return path
-
-
-def _cuda(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a))).cuda()
 
 
 @pytest.mark.parametrize("extra", [("--device-rate", "48000"), ("--loop", "4"), ("--world", "2")])

@@ -28,11 +28,10 @@ def fmt_chunk(fmt, channels, sr, bits, style="plain"):
 
 
 def wav_image(data: bytes, fmt=1, channels=2, sr=48000, bits=16, style="plain", extra_before=b"",
-              split_data=None, data_size=None) -> bytes:
+              split_data=None, data_size=None, between=b"") -> bytes:
     body = b"WAVE" + fmt_chunk(fmt, channels, sr, bits, style) + extra_before
-    if split_data:
-        for a, b in split_data:
-            body += chunk(b"data", data[a:b])
+    if split_data:  # (`between`: whole chunks that separate the data chunks)
+        body += between.join(chunk(b"data", data[a:b]) for a, b in split_data)
     else:
         body += chunk(b"data", data, data_size)
     return b"RIFF" + struct.pack("<I", len(body)) + body
