@@ -77,6 +77,14 @@
 //     --deconv-pre N    output samples of negative time (0): where a sweep's
 //                       harmonic responses land
 //     --ir-length N     samples written (min(n, 2^20): usable by --convolve)
+//     --psd OUT.csv     also write the average spectrum of the written render
+//                       (dsp_welch, Hann 8192 / 4096, one-sided density): a
+//                       header line, then per bin its frequency in Hz and each
+//                       channel's 10 log10(PSD), dB re full scale^2 / Hz.  Prints
+//                       one JSON line {"psd": {frames, bins, hop, channels:
+//                       [{peak_hz, peak_db, power_db}]}}.  A render shorter than
+//                       one frame is an error.  Not with --deconvolve, --loop or
+//                       the multi-GPU modes
 //     --loop NBLOCKS    loop mode (audio.cpp:100-132): NBLOCKS blocks from a
 //                       file that wraps around (no --stft)
 //   multi-GPU (cfg 5, shard.h): one process per GPU, channels sharded one
@@ -97,8 +105,17 @@
 //   with 10 ms fades) as a mono WAV: the excitation of a measurement that
 //   --deconvolve evaluates.  Host only: no device is opened.
 //
+// dspbench_render REC.wav OUT.csv --transfer REF.wav
+//   the transfer function from the first channel of REF.wav to each channel of
+//   REC.wav (dsp_welch with a reference, Hann 8192 / 4096; dsp_welch_derive):
+//   OUT.csv holds a header line, then per bin its frequency in Hz and per
+//   channel |H1| in dB, H1's phase in radians and the coherence.  Prints one
+//   JSON line {"transfer": {frames, bins, hop, channels: [{mean_coherence,
+//   min_coherence, gain_db}]}}.  Nothing is resampled or aligned: files of
+//   different rates or lengths, or shorter than one frame, are refused.
+//
 // options.cpp reads the command line, device.hpp owns what lives on the device,
-// wavio.cpp is the one WAV loader and the one writer; here are the three modes.
+// wavio.cpp is the one WAV loader and the one writer; here are the four modes.
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -259,6 +276,158 @@ int run_deconvolve(const Options &o) {
     if (int e = write_file(o.out_path.c_str(), {{w.bytes.data(), w.size}})) return e;
     std::printf("dspbench_render: %s deconvolved by %s: %u ch x %llu frames @ %u Hz -> %s (n = %u), %.1f ms end to end\n",
                 o.in_path.c_str(), ref_path, Cf, (unsigned long long)irl, rate, o.out_path.c_str(), n, dev.ms());
+    return 0;
+}
+
+// ---- --psd / --transfer: Welch sums of device rows, on the host ---------------
+struct WelchSums {
+    uint64_t frames = 0;
+    double win_sum = 0.0, win_sumsq = 0.0;
+    std::vector<double> sxx, srr, sxy;  // [C][K], [K], [C][2 K]
+};
+
+// dsp_welch (Hann 8192 / 4096) of C rows of L samples, with the row ref when there is one
+int welch_sums(float *const *rows, uint32_t C, uint64_t L, const float *ref, Device &dev, WelchSums &w) {
+    int st = dsp_welch_plan(L, C, ref != nullptr, nullptr, &w.frames, nullptr, nullptr, nullptr, &w.win_sum, &w.win_sumsq);
+    if (st) return fail("dsp_welch_plan", st);
+    const size_t per = (size_t)K * (ref ? 3 : 1);  // doubles per channel: sxx, then sxy
+    DevBuf buf;
+    HIPCK(hipMalloc(&buf.h, ((size_t)C * per + K) * sizeof(double)));
+    double *base = (double *)buf.h, *drr = base + (size_t)C * per;
+    std::vector<double *> dxx(C), dxy(C);
+    for (uint32_t c = 0; c < C; ++c) dxx[c] = base + c * per, dxy[c] = dxx[c] + K;
+    if ((st = dsp_welch(rows, C, L, ref, dxx.data(), ref ? drr : nullptr, ref ? dxy.data() : nullptr, nullptr, &dev.ex)))
+        return fail("dsp_welch", st);
+    std::vector<double> host((size_t)C * per + K);
+    HIPCK(hipMemcpyAsync(host.data(), base, host.size() * sizeof(double), hipMemcpyDeviceToHost, dev.stream.h));
+    HIPCK(hipStreamSynchronize(dev.stream.h));
+    w.sxx.resize((size_t)C * K);
+    if (ref) w.sxy.resize((size_t)C * 2 * K), w.srr.assign(host.end() - K, host.end());
+    for (uint32_t c = 0; c < C; ++c) {
+        std::copy_n(host.begin() + c * per, K, w.sxx.begin() + (size_t)c * K);
+        if (ref) std::copy_n(host.begin() + c * per + K, 2 * K, w.sxy.begin() + (size_t)c * 2 * K);
+    }
+    return 0;
+}
+
+// row pointers into a [C][n] vector
+std::vector<double *> row_table(std::vector<double> &v, uint32_t C, size_t n) {
+    std::vector<double *> t(C);
+    for (uint32_t c = 0; c < C; ++c) t[c] = v.data() + c * n;
+    return t;
+}
+
+// a CSV: the header line, then per bin its frequency and `cols` values
+int write_csv(const char *path, const std::string &header, uint32_t rate, const std::vector<std::vector<double>> &cols) {
+    std::string s = header + "\n";
+    char b[48];
+    for (uint32_t k = 0; k < K; ++k) {
+        std::snprintf(b, sizeof b, "%.9g", (double)k * (double)rate / (double)N);
+        s += b;
+        for (const auto &col : cols) std::snprintf(b, sizeof b, ",%.9g", col[k]), s += b;
+        s += "\n";
+    }
+    return write_file(path, {{s.data(), s.size()}});
+}
+
+// --psd: the average spectrum of rows (the render) as dB re full scale^2 / Hz, and its JSON line
+int write_psd(const Options &o, float *const *rows, uint32_t C, uint64_t L, uint32_t rate, Device &dev) {
+    WelchSums w;
+    if (int e = welch_sums(rows, C, L, nullptr, dev, w)) return e;
+    std::vector<double> psd((size_t)C * K);
+    const std::vector<double *> xx = row_table(w.sxx, C, K), pp = row_table(psd, C, K);
+    int st = dsp_welch_derive(xx.data(), nullptr, nullptr, C, K, w.frames, (double)rate, w.win_sum, w.win_sumsq, 0,
+                              pp.data(), nullptr, nullptr);
+    if (st) return fail("dsp_welch_derive", st);
+    std::string header = "hz", j = "{\"psd\": {\"frames\": " + std::to_string(w.frames) + ", \"bins\": " +
+                                   std::to_string(K) + ", \"hop\": " + std::to_string(H) + ", \"channels\": [";
+    std::vector<std::vector<double>> cols(C, std::vector<double>(K));
+    for (uint32_t c = 0; c < C; ++c) {
+        header += ",ch" + std::to_string(c) + "_db";
+        uint32_t at = 0;
+        double power = 0.0;  // the integral of the density: the mean square of the windowed signal
+        for (uint32_t k = 0; k < K; ++k) {
+            const double v = pp[c][k];
+            cols[c][k] = 10.0 * std::log10(v);
+            power += v * (double)rate / (double)N;
+            if (v > pp[c][at]) at = k;
+        }
+        j += std::string(c ? ", " : "") + "{\"peak_hz\": " + json_num((double)at * rate / N) + ", \"peak_db\": " +
+             json_num(cols[c][at]) + ", \"power_db\": " + json_num(10.0 * std::log10(power)) + "}";
+    }
+    if (int e = write_csv(o.psd_path.c_str(), header, rate, cols)) return e;
+    std::printf("%s]}}\n", j.c_str());
+    return 0;
+}
+
+// ---- --transfer: H1 and coherence from REF's first channel to the recording ---
+int run_transfer(const Options &o) {
+    Device dev(o.device);
+    Wav in, ref;
+    if (int e = load_wav(o.in_path.c_str(), "", [&](const dsp_wav_info &i) {
+            if (i.channels == 0 || i.channels > 16) {
+                std::fprintf(stderr, "dspbench_render: %u file channels (1..16 supported)\n", i.channels);
+                return 1;
+            }
+            if (i.frames < N) {
+                std::fprintf(stderr, "dspbench_render: --transfer: %s has %llu frames, fewer than one %u-point frame\n",
+                             o.in_path.c_str(), (unsigned long long)i.frames, N);
+                return 1;
+            }
+            return 0;
+        }, dev, in))
+        return e;
+    const uint32_t C = in.info.channels, rate = in.info.sample_rate;
+    const uint64_t L = in.info.frames;
+    const char *ref_path = o.transfer_path.c_str();
+    if (int e = load_wav(ref_path, " (reference)", [&](const dsp_wav_info &ri) {
+            if (ri.sample_rate != rate) {
+                std::fprintf(stderr, "dspbench_render: --transfer: %s is at %u Hz, %s at %u Hz\n", ref_path, ri.sample_rate,
+                             o.in_path.c_str(), rate);
+                return 1;
+            }
+            if (ri.frames != L || ri.channels == 0 || ri.channels > 16) {
+                std::fprintf(stderr, "dspbench_render: --transfer: %s has %llu frames, %s %llu (nothing is resampled or "
+                                     "aligned)\n", ref_path, (unsigned long long)ri.frames, o.in_path.c_str(),
+                             (unsigned long long)L);
+                return 1;
+            }
+            return 0;
+        }, dev, ref))
+        return e;
+    WelchSums w;
+    if (int e = welch_sums(in.rows.ptr.data(), C, L, ref.rows.ptr[0], dev, w)) return e;
+    std::vector<double> h1((size_t)C * 2 * K), coh((size_t)C * K);
+    const std::vector<double *> xx = row_table(w.sxx, C, K), xy = row_table(w.sxy, C, 2 * K), hh = row_table(h1, C, 2 * K),
+                                cc = row_table(coh, C, K);
+    int st = dsp_welch_derive(xx.data(), w.srr.data(), xy.data(), C, K, w.frames, (double)rate, w.win_sum, w.win_sumsq, 0,
+                              nullptr, hh.data(), cc.data());
+    if (st) return fail("dsp_welch_derive", st);
+    std::string header = "hz", j = "{\"transfer\": {\"frames\": " + std::to_string(w.frames) + ", \"bins\": " +
+                                   std::to_string(K) + ", \"hop\": " + std::to_string(H) + ", \"channels\": [";
+    std::vector<std::vector<double>> cols;
+    double rr = 0.0;
+    for (uint32_t k = 0; k < K; ++k) rr += w.srr[k];
+    for (uint32_t c = 0; c < C; ++c) {
+        const std::string n = "ch" + std::to_string(c);
+        header += "," + n + "_h1_db," + n + "_phase_rad," + n + "_coherence";
+        std::vector<double> db(K), ph(K), g(cc[c], cc[c] + K);
+        double mean = 0.0, low = 1.0, power = 0.0;
+        for (uint32_t k = 0; k < K; ++k) {
+            const double re = hh[c][2 * k], im = hh[c][2 * k + 1];
+            db[k] = 20.0 * std::log10(std::hypot(re, im));
+            ph[k] = std::atan2(im, re);
+            mean += g[k] / K, low = std::min(low, g[k]), power += xx[c][k];
+        }
+        j += std::string(c ? ", " : "") + "{\"mean_coherence\": " + json_num(mean) + ", \"min_coherence\": " + json_num(low) +
+             ", \"gain_db\": " + json_num(10.0 * std::log10(power / rr)) + "}";
+        cols.push_back(std::move(db)), cols.push_back(std::move(ph)), cols.push_back(std::move(g));
+    }
+    if (int e = write_csv(o.out_path.c_str(), header, rate, cols)) return e;
+    std::printf("%s]}}\n", j.c_str());
+    std::printf("dspbench_render: %s against %s: %u ch x %llu frames @ %u Hz, %llu Welch frames -> %s, %.1f ms end to end\n",
+                o.in_path.c_str(), ref_path, C, (unsigned long long)L, rate, (unsigned long long)w.frames,
+                o.out_path.c_str(), dev.ms());
     return 0;
 }
 
@@ -563,6 +732,11 @@ int run_render(const Options &o, time_t started) {
             return e;
     r.nblocks = o.loop_blocks ? o.loop_blocks : (r.L + o.block - 1) / o.block;
     r.Lr = r.nblocks * o.block;
+    if (!o.psd_path.empty() && r.Lr < N) {
+        std::fprintf(stderr, "dspbench_render: --psd: the render has %llu frames, fewer than one %u-point frame\n",
+                     (unsigned long long)r.Lr, N);
+        return 1;
+    }
     HIPCK(r.out.alloc(r.C, r.Lr));
     r.mag.ptr.assign(r.C, nullptr);  // (--loop computes no spectra: with --stft their copy fails, as it always has)
     if (int e = make_plugin(r)) return e;
@@ -571,6 +745,8 @@ int run_render(const Options &o, time_t started) {
     if (o.loudness || o.normalize)
         if (int e = level(r)) return e;
     if (int e = write_outputs(r)) return e;
+    if (!o.psd_path.empty())  // of what was written: after --normalize and --limit
+        if (int e = write_psd(o, r.out.ptr.data(), r.C, r.Lr, r.rate, r.dev)) return e;
     if (r.comm) dsp_comm_destroy(r.comm);
     return 0;
 }
@@ -591,6 +767,7 @@ int main(int argc, char **argv) {
     switch (p.opt.mode) {
     case Options::SWEEP: return run_sweep(p.opt);
     case Options::DECONVOLVE: return run_deconvolve(p.opt);
+    case Options::TRANSFER: return run_transfer(p.opt);
     default: return run_render(p.opt, started);
     }
 }

@@ -43,6 +43,8 @@ const struct {
     {"--deconv-eps", true, f64<&O::deconv_eps>},
     {"--deconv-pre", true, u64<&O::deconv_pre>},
     {"--ir-length", true, u64_nonzero<&O::ir_length>},
+    {"--psd", true, text<&O::psd_path>},
+    {"--transfer", true, text<&O::transfer_path>},
     {"--gain", true, f32<&O::gain>},
     {"--ir", true, ir_pair},
     {"--block", true, u32<&O::block>},
@@ -81,6 +83,15 @@ const struct {
      "--loudness, --normalize and the multi-GPU modes\n", true},
     {[](const O &o) { return o.deconv_path.empty() && o.deconv_options(); },
      "dspbench_render: --deconv-eps, --deconv-pre and --ir-length need --deconvolve\n", true},
+    {[](const O &o) {
+         return !o.transfer_path.empty() &&
+                (o.have_plugin || !o.conv_path.empty() || !o.deconv_path.empty() || o.loop_blocks || o.multi_gpu() ||
+                 o.rate || !o.stft_path.empty() || !o.psd_path.empty() || o.levels() || !o.bits.empty());
+     },
+     "dspbench_render: --transfer excludes --plugin, --convolve, --deconvolve, --loop, --stft, --psd, --rate, --bits, "
+     "--loudness, --normalize and the multi-GPU modes\n", true},
+    {[](const O &o) { return !o.psd_path.empty() && (!o.deconv_path.empty() || o.loop_blocks || o.multi_gpu()); },
+     "dspbench_render: --psd excludes --deconvolve, --loop and the multi-GPU modes\n", true},
     {[](const O &o) { return o.rate && (o.dev_rate || o.loop_blocks || o.multi_gpu()); },
      "dspbench_render: --rate excludes --device-rate, --loop and the multi-GPU modes\n", true},
     {[](const O &o) { return o.levels() && (o.loop_blocks || o.multi_gpu()); },
@@ -131,7 +142,9 @@ const char *usage_text() {
            "       [--loudness] [--normalize LUFS [--true-peak-ceiling DBTP [--limit]]]\n"
            "       [--limit-lookahead MS] [--limit-release MS]\n"
            "       [--deconvolve REF.wav [--deconv-eps E] [--deconv-pre N] [--ir-length N]]\n"
+           "       [--psd OUT.csv]\n"
            "       [--world W --rank R --comm-id FILE [--run-id STR] [--chunk SAMPLES]]\n"
+           "       dspbench_render REC.wav OUT.csv --transfer REF.wav [--device N]\n"
            "       dspbench_render --sweep F1:F2:SECONDS[:RATE[:BITS]] OUT.wav\n";
 }
 
@@ -154,6 +167,7 @@ Parsed parse_options(int argc, const char *const *argv, const Env &env) {
         if (opt == std::end(kOptions) || (opt->takes_value && ++i == argc) || !opt->read(o, argv[i])) return usage_error();
     }
     if (!o.deconv_path.empty()) o.mode = Options::DECONVOLVE;
+    else if (!o.transfer_path.empty()) o.mode = Options::TRANSFER;
     if (o.multi()) {  // torchrun-style environment when not given explicitly
         if (!o.world) o.world = env.world_size ? (uint32_t)std::atoi(env.world_size) : 1;
         if (!o.have_rank) o.rank = env.rank ? (uint32_t)std::atoi(env.rank) : 0;

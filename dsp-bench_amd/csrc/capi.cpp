@@ -132,23 +132,12 @@ int get_delta(int dev, hipStream_t s, const float **out) {
     return st;
 }
 
-// the cosine windows w[n] = a - b cos(2 pi n / (valid - 1))
-static void window_coefficients(int kind, double *a, double *b) {
-    *a = 0.54, *b = 0.46;
-    if (kind == DSP_WIN_HANN) *a = 0.5, *b = 0.5;
-    else if (kind == DSP_WIN_RECT) *a = 1.0, *b = 0.0;
-}
-
 int get_window(int dev, hipStream_t s, int kind, uint32_t N, uint32_t valid, const float **out, double scale) {
     std::lock_guard<std::mutex> lk(g_mu);
     float *&slot = g_res[dev].windows[std::make_tuple(kind, N, valid, (float)scale)];
     const int st = first_use_table(slot, s, "a window table", [&] {
-        double a, b;
-        window_coefficients(kind, &a, &b);
-        std::vector<float> h(N, 0.f);
-        for (uint32_t n = 0; n < valid; ++n)
-            h[n] = valid == 1 ? (float)scale
-                              : (float)(scale * (a - b * std::cos(2.0 * M_PI * (double)n / (double)(valid - 1))));
+        std::vector<float> h(N);
+        window_table(kind, N, valid, scale, h.data());  // (host_tables.cpp)
         return h;
     });
     *out = slot;

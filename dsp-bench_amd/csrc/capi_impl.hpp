@@ -210,6 +210,7 @@ enum ScratchSlot : int {
     kScratchLimiter = 4,     // a dsp_limiter call's hold rows, tile aggregates, carries and result words
     kScratchBigFft = 5,      // a dsp_rfft / dsp_irfft / dsp_deconvolve channel group's work buffers and spectra
     kScratchSpectrumHop = 6, // the hop the one-frame launch of a spectrum-row miss renders beside its row
+    kScratchWelch = 7,       // a dsp_welch channel group's chunk of spectra and its runs' partial sums
 };
 int get_scratch(int dev, hipStream_t s, size_t bytes, float **out, ScratchSlot slot);
 

@@ -1,14 +1,15 @@
 // capi_signal.cpp -- the Plugin-free row calls of the C ABI
 // (include/dspbench/dspbench.h): dsp_resample, dsp_loudness, dsp_limiter,
-// dsp_rfft / dsp_irfft, dsp_deconvolve and dsp_sweep, with their plans.  Each
-// checks its arguments and its rows' layout before it looks at a device, holds
-// its cached tables until its launches are enqueued, and walks its channels in
-// groups of kMaxChannels.  What it shares with capi.cpp and capi_render.cpp is
-// in capi_impl.hpp.
+// dsp_rfft / dsp_irfft, dsp_deconvolve, dsp_sweep and dsp_welch, with their
+// plans.  Each checks its arguments and its rows' layout before it looks at a
+// device, holds its cached tables until its launches are enqueued, and walks
+// its channels in groups of kMaxChannels.  What it shares with capi.cpp and
+// capi_render.cpp is in capi_impl.hpp.
 #include "capi_impl.hpp"
 #include "limiter_host.hpp"
 #include "loudness_host.hpp"
 #include "sweep_host.hpp"
+#include "welch_host.hpp"
 
 namespace dspb {
 
@@ -89,6 +90,25 @@ static int sweep_plan_checked(uint32_t sr, const dsp_sweep_spec *spec, SweepPlan
     const char *why = nullptr;
     const int r = sweep_plan(sr, spec, p, &why);
     return plan_status(r ? 1 : 0, why);  // (every refusal is the spec's: invalid)
+}
+
+static_assert(kWelchGroup == kMaxChannels, "welch_plan sizes the scratch for for_groups' channel groups");
+static int welch_plan_checked(uint64_t L, uint32_t C, int has_ref, const dsp_welch_spec *spec, WelchPlan *p) {
+    const char *why = nullptr;
+    const int r = welch_plan(L, C, has_ref, spec, p, &why);
+    return plan_status(r, why);
+}
+
+// dsp_welch's float64 output rows: none NULL, each 8-byte aligned; *out = the rows as float rows
+static int welch_double_rows(const char *name, double *const *rows, uint32_t C, std::vector<const float *> *out) {
+    if (!rows) return invalid("%s is NULL", name);
+    out->resize(C);
+    for (uint32_t c = 0; c < C; ++c) {
+        if (!rows[c]) return invalid("%s[%u] is NULL", name, c);
+        if (!aligned(rows[c], 8)) return invalid("dsp_welch: %s[%u] is not 8-byte aligned", name, c);
+        (*out)[c] = reinterpret_cast<const float *>(rows[c]);
+    }
+    return DSP_OK;
 }
 
 // A call's large-FFT context (fft_big.hip): the hold on n's cached twiddle
@@ -637,6 +657,113 @@ int dsp_sweep_harmonic_offset(uint32_t sr, const dsp_sweep_spec *spec, uint32_t 
     if (int st = sweep_plan_checked(sr, spec, &p)) return st;
     if (order == 0) return invalid("dsp_sweep_harmonic_offset: order must be >= 1");
     if (samples) *samples = sweep_harmonic_offset(sr, p, order);
+    return DSP_OK;
+}
+
+int dsp_welch_plan(uint64_t L, uint32_t C, int has_ref, const dsp_welch_spec *spec, uint64_t *frames, uint32_t *bins,
+                   uint32_t *run, uint64_t *scratch_bytes, double *win_sum, double *win_sumsq) {
+    WelchPlan p;
+    if (int st = welch_plan_checked(L, C, has_ref, spec, &p)) return st;
+    if (frames) *frames = p.frames;
+    if (bins) *bins = kWelchBins;
+    if (run) *run = kWelchRun;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    if (win_sum) *win_sum = p.win_sum;
+    if (win_sumsq) *win_sumsq = p.win_sumsq;
+    return DSP_OK;
+}
+
+int dsp_welch(const float *const *in, uint32_t C, uint64_t L, const float *ref, double *const *sxx, double *srr,
+              double *const *sxy, const dsp_welch_spec *spec, const dsp_exec *ex) {
+    WelchPlan p;
+    int st;
+    if ((st = welch_plan_checked(L, C, ref != nullptr, spec, &p))) return st;
+    if ((st = whole_rows_only(ex, "dsp_welch"))) return st;
+    if ((srr != nullptr) != (ref != nullptr) || (sxy != nullptr) != (ref != nullptr))
+        return invalid("dsp_welch: srr and sxy go with ref (all three, or none)");
+    if ((st = check_rows("in", in, C))) return st;
+    // the float64 rows as float rows of twice the length, for the layout checks
+    std::vector<const float *> fxx, fxy;
+    if ((st = welch_double_rows("sxx", sxx, C, &fxx)) || (ref && (st = welch_double_rows("sxy", sxy, C, &fxy)))) return st;
+    const float *frr = reinterpret_cast<const float *>(srr);
+    if (ref && !aligned(srr, 8)) return invalid("dsp_welch: srr is not 8-byte aligned");
+    {
+        const uint32_t nr = ref ? 1u : 0u;
+        const Rows I{in, C, L}, Rf{&ref, nr, L}, XX{fxx.data(), C, 2ull * kWelchBins},
+            XY{fxy.data(), ref ? C : 0u, 4ull * kWelchBins}, RR{&frr, nr, 2ull * kWelchBins};
+        if (rows_overlap(I, XX) || rows_overlap(I, XY) || rows_overlap(I, RR) || rows_overlap(Rf, XX) ||
+            rows_overlap(Rf, XY) || rows_overlap(Rf, RR) || rows_overlap(XX, XY) || rows_overlap(XX, RR) ||
+            rows_overlap(XY, RR) || rows_overlap_each_other(XX) || rows_overlap_each_other(XY))
+            return invalid("dsp_welch: an output row overlaps an input row or another output row");
+    }
+    DeviceGuard g(ex);
+    if (g.status) return g.status;
+    hipStream_t s = stream_of(ex);
+    Stage stage(ex);
+    const std::vector<const float *> din = stage.in_rows(in, C, L);
+    const float *dref = ref ? stage.in(ref, L) : nullptr;
+    std::vector<double *> dxx(C), dxy(C, nullptr);
+    for (uint32_t c = 0; c < C; ++c) {
+        dxx[c] = (double *)stage.out_bytes(sxx[c], sizeof(double) * kWelchBins);
+        if (ref) dxy[c] = (double *)stage.out_bytes(sxy[c], sizeof(double) * 2 * kWelchBins);
+    }
+    double *drr = ref ? (double *)stage.out_bytes(srr, sizeof(double) * kWelchBins) : nullptr;
+    if (stage.status) return stage.status;
+
+    WelchArgs A{};
+    const float *win = nullptr;
+    if ((st = get_tw(g.dev, s, &A.tw)) || (st = get_window(g.dev, s, p.window, kWelchN, kWelchN, &win))) return st;
+    float *scratch = nullptr;
+    if ((st = get_scratch(g.dev, s, p.scratch_bytes, &scratch, kScratchWelch))) return st;
+    char *base = reinterpret_cast<char *>(scratch);
+    A.win2 = reinterpret_cast<const v2f *>(win);
+    A.ref = dref;
+    A.has_ref = ref ? 1u : 0u;
+    A.H = p.H;
+    A.chunk = p.chunk;
+    A.runs_cap = p.runs_cap;
+    A.S = reinterpret_cast<float4 *>(base);
+    A.pxx = reinterpret_cast<v2f *>(base + p.off_pxx);
+    A.pxy = reinterpret_cast<float4 *>(base + p.off_pxy);
+    A.prr = reinterpret_cast<v2f *>(base + p.off_prr);
+    st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
+        WelchArgs G = A;
+        G.cn = cn;
+        for (uint32_t j = 0; j < cn; ++j) {
+            G.in.p[j] = din[c0 + j];
+            G.sxx[j] = dxx[c0 + j];
+            G.sxy[j] = dxy[c0 + j];
+        }
+        G.srr = c0 == 0 ? drr : nullptr;  // the reference's own sums: once
+        for (uint64_t f0 = 0; f0 < p.frames; f0 += p.chunk) {
+            G.f0 = f0;
+            G.nf = (uint32_t)std::min<uint64_t>(p.frames - f0, p.chunk);
+            G.first = f0 == 0;
+            if (int e = launch_welch_chunk(G, s)) return e;
+        }
+        return (int)DSP_OK;
+    });
+    if (st) return st;
+    return (st = stage.copy_back()) ? st : finish(ex);
+}
+
+int dsp_welch_derive(const double *const *sxx, const double *srr, const double *const *sxy, uint32_t C, uint32_t bins,
+                     uint64_t frames, double sr, double win_sum, double win_sumsq, uint32_t flags, double *const *psd,
+                     double *const *H1, double *const *coherence) {
+    if (C == 0 || bins == 0 || frames == 0) return invalid("dsp_welch_derive: needs C >= 1, bins >= 1 and frames >= 1");
+    if (flags & ~DSP_WELCH_SPECTRUM) return invalid("dsp_welch_derive: unknown flags");
+    const bool cross = H1 || coherence;
+    if ((psd || coherence) && !sxx) return invalid("sxx is NULL");
+    if (cross && (!srr || !sxy)) return invalid("dsp_welch_derive: H1 and coherence need srr and sxy");
+    for (uint32_t c = 0; c < C; ++c)
+        if ((sxx && !sxx[c]) || (cross && !sxy[c]) || (psd && !psd[c]) || (H1 && !H1[c]) || (coherence && !coherence[c]))
+            return invalid("dsp_welch_derive: row %u is NULL", c);
+    if (psd) {
+        const double scale = (flags & DSP_WELCH_SPECTRUM) ? win_sum * win_sum : sr * win_sumsq;
+        if (!std::isfinite(scale) || scale <= 0.0)
+            return invalid("dsp_welch_derive: the scale (sr, win_sum, win_sumsq) must be finite and positive");
+    }
+    welch_derive(sxx, srr, sxy, C, bins, frames, sr, win_sum, win_sumsq, flags, psd, H1, coherence);
     return DSP_OK;
 }
 

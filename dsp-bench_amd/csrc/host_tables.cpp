@@ -13,6 +13,21 @@ namespace dspb {
 //   (Re H[k1], Re H[k2], Im H[k1], Im H[k2], Re H[M-k1], Re H[M-k2], Im H[M-k1], Im H[M-k2])
 // with k1 = l + 64 ka, k2 = k1 + 1024, M = 4096; then H[2048] (re, im).
 // FFT_n(taps zero-padded) in float64 (iterative radix-2, forward e^-i)
+void window_coefficients(int kind, double *a, double *b) {
+    *a = 0.54, *b = 0.46;
+    if (kind == 1) *a = 0.5, *b = 0.5;        // DSP_WIN_HANN
+    else if (kind == 2) *a = 1.0, *b = 0.0;   // DSP_WIN_RECT
+}
+
+void window_table(int kind, uint32_t N, uint32_t valid, double scale, float *h) {
+    double a, b;
+    window_coefficients(kind, &a, &b);
+    for (uint32_t n = 0; n < N; ++n)
+        h[n] = n >= valid ? 0.f
+               : valid == 1 ? (float)scale
+                            : (float)(scale * (a - b * std::cos(2.0 * M_PI * (double)n / (double)(valid - 1))));
+}
+
 void taps_spectrum(const float *taps, uint32_t T, int n, std::vector<double> &re, std::vector<double> &im) {
     re.assign(n, 0.0);
     im.assign(n, 0.0);

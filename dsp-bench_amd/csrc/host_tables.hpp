@@ -9,6 +9,12 @@ namespace dspb {
 
 constexpr uint32_t kIirPairSections = 2;  // cascades of >= this many sections: channel pairs per wave
 
+// the cosine windows w[n] = a - b cos(2 pi n / (valid - 1)) (dspbench.h dsp_window; anything else: Hamming)
+void window_coefficients(int kind, double *a, double *b);
+// The one window table (capi.cpp get_window's device tables, welch_host.cpp's
+// sums): length `valid`, symmetric (ref ippsWinHamming_32f convention), times
+// `scale`, zero-padded to N.  Computed in double, rounded once to float.
+void window_table(int kind, uint32_t N, uint32_t valid, double scale, float *h);
 // FFT_n(taps zero-padded) in float64 (iterative radix-2, forward e^-i)
 void taps_spectrum(const float *taps, uint32_t T, int n, std::vector<double> &re, std::vector<double> &im);
 // the 8192-point table of fir_fft_kernel: 8192 + 2 floats

@@ -261,6 +261,30 @@ int launch_deconv_max(const v2f *S, uint32_t bins, uint32_t *word, hipStream_t s
 // Y_j[k] = Y_j[k] conj(S[k]) / (|S[k]|^2 + eps *word) for j < nch spectra of `bins` bins at Y + j bins
 int launch_deconv_divide(v2f *Y, const v2f *S, uint32_t bins, uint32_t nch, float eps, const uint32_t *word,
                          hipStream_t s);
+// dsp_welch (welch.hip): one chunk of frames of one channel group per call:
+// forward transforms into S, the run sums into the partials, the runs added in
+// float64 onto the output rows (welch_host.hpp has the constants and the layout)
+struct WelchArgs {
+    ChanIn in;             // cn channel rows
+    const float *ref;      // the reference row (row cn of the launches), or NULL
+    uint32_t cn, has_ref;
+    uint64_t f0;           // the chunk's first frame
+    uint32_t nf;           // its frames, <= chunk
+    uint32_t H;
+    uint32_t chunk;        // frames per row of S
+    uint32_t runs_cap;     // runs per row of the partials: chunk / kWelchRun
+    const v2f *win2;       // the window as 4096 float2 (w[2m], w[2m+1])
+    const v2f *tw;         // T8192 + lane-major stage twiddles (capi.cpp get_tw)
+    float4 *S;             // [cn + has_ref][chunk] spectra of kWelchSpec4 float4
+    v2f *pxx;              // [cn][runs_cap][kWelchSpec4]
+    float4 *pxy;           // [cn][runs_cap][kWelchSpec4] (re, re, im, im)
+    v2f *prr;              // [runs_cap][kWelchSpec4]
+    double *sxx[kMaxChannels];  // output rows: 4097 doubles,
+    double *sxy[kMaxChannels];  // 4097 (re, im) pairs (has_ref),
+    double *srr;           // 4097 doubles (has_ref; NULL: a later channel group, not written again)
+    uint32_t first;        // the call's first chunk: the sums start from zero
+};
+int launch_welch_chunk(const WelchArgs &A, hipStream_t s);
 int launch_minmax(const float *x, uint64_t n, uint32_t P, float *vmax, float *vmin, hipStream_t s);
 int launch_spectro(const float *mag, uint64_t F, uint32_t K, uint64_t ld, uint32_t P, float *out,
                    hipStream_t s);

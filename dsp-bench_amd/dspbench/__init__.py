@@ -8,11 +8,13 @@ from .api import (IR_BUFFER_LENGTH, Plugin, conv_plan, deconv_plan, deconvolve, 
                   k_weighting, limiter, limiter_plan, loudness, loudness_gate, loudness_plan, minmax_decimate, num_blocks,
                   render_loop, render_offline, render_stft, render_stft_host,
                   resample, resample_plan, resample_taps, irfft, rfft, rfft_plan, spectrogram_decimate,
-                  stft_frames, stft_magnitude, sweep, sweep_harmonic_offset, sweep_plan)
+                  stft_frames, stft_magnitude, sweep, sweep_harmonic_offset, sweep_plan,
+                  csd, transfer, welch, welch_derive, welch_plan, welch_sums)
 from . import module, shard, wav  # noqa: F401
 
 __all__ = ["Plugin", "render_offline", "render_loop", "render_stft_host", "minmax_decimate", "spectrogram_decimate", "stft_magnitude", "render_stft", "ir_analysis",
            "fft_forward", "fft_reverse", "conv_plan", "resample", "resample_plan", "resample_taps", "stft_frames", "num_blocks", "lib", "DspError",
            "loudness", "loudness_plan", "loudness_gate", "k_weighting", "limiter", "limiter_plan",
            "rfft", "irfft", "rfft_plan", "deconvolve", "deconv_plan", "sweep", "sweep_plan", "sweep_harmonic_offset",
+           "welch", "csd", "transfer", "welch_plan", "welch_sums", "welch_derive",
            "DSP_WIN_HAMMING", "DSP_WIN_HANN", "DSP_WIN_RECT", "IR_BUFFER_LENGTH", "shard", "wav", "module"]

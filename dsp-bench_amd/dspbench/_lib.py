@@ -97,7 +97,14 @@ class dsp_sweep_spec(C.Structure):
                 ("fade", C.c_uint32)]
 
 
+class dsp_welch_spec(C.Structure):
+    _fields_ = [("N", C.c_uint32), ("H", C.c_uint32), ("window", C.c_int32)]
+
+
+DSP_WELCH_SPECTRUM = 0x1
+
 DPP = C.POINTER(C.POINTER(C.c_double))
+DP = C.POINTER(C.c_double)
 
 DSP_WAV_FORMAT_PCM = 1
 DSP_WAV_FORMAT_FLOAT = 3
@@ -207,6 +214,12 @@ _SIGS = {
     "dsp_sweep_plan": (C.c_int, [C.c_uint32, C.POINTER(dsp_sweep_spec), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "dsp_sweep": (C.c_int, [C.c_uint32, C.POINTER(dsp_sweep_spec), FP, C.c_uint64]),
     "dsp_sweep_harmonic_offset": (C.c_int, [C.c_uint32, C.POINTER(dsp_sweep_spec), C.c_uint32, C.POINTER(C.c_double)]),
+    "dsp_welch_plan": (C.c_int, [C.c_uint64, C.c_uint32, C.c_int, C.POINTER(dsp_welch_spec), C.POINTER(C.c_uint64),
+                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), DP, DP]),
+    "dsp_welch": (C.c_int, [FPP, C.c_uint32, C.c_uint64, FP, DPP, DP, DPP, C.POINTER(dsp_welch_spec),
+                            C.POINTER(dsp_exec)]),
+    "dsp_welch_derive": (C.c_int, [DPP, DP, DPP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_double, C.c_double,
+                                   C.c_double, C.c_uint32, DPP, DPP, DPP]),
     "dsp_render_offline": (C.c_int, [FPP, C.c_uint32, C.c_uint64, FPP, C.c_uint32, C.c_uint32,
                                      C.c_float, C.POINTER(dsp_plugin), C.POINTER(dsp_exec)]),
     "dsp_render_loop": (C.c_int, [FPP, C.c_uint32, C.c_uint64, C.c_uint64, FPP, C.c_uint32, C.c_uint32,

@@ -428,6 +428,138 @@ def sweep_harmonic_offset(sr: int, f1: float, f2: float, seconds: float, order: 
     return v.value
 
 
+_WELCH_WINDOWS = {"hann": L.DSP_WIN_HANN, "hamming": L.DSP_WIN_HAMMING}
+
+
+def _welch_spec(hop, window, N=8192):
+    w = _WELCH_WINDOWS.get(window, window) if isinstance(window, str) else window
+    if isinstance(w, str):
+        raise ValueError(f"window {window!r}: 'hann' or 'hamming' (the symmetric tables of stft_magnitude)")
+    return L.dsp_welch_spec(N, hop, w)
+
+
+def welch_plan(L_: int, channels: int = 1, has_ref: bool = False, hop: int = 4096, window="hann", N: int = 8192) -> dict:
+    """dsp_welch_plan (host only): frames, bins, the run length of the summation
+    order, the device scratch bytes, and the window's sum and sum of squares."""
+    sp = _welch_spec(hop, window, N)
+    f, b, r, sb, ws, wq = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_double(), C.c_double()
+    check(L.lib().dsp_welch_plan(L_, channels, int(has_ref), C.byref(sp), C.byref(f), C.byref(b), C.byref(r),
+                                 C.byref(sb), C.byref(ws), C.byref(wq)), "dsp_welch_plan")
+    return {"frames": f.value, "bins": b.value, "run": r.value, "scratch_bytes": sb.value, "win_sum": ws.value,
+            "win_sumsq": wq.value}
+
+
+def _f64_like(ref, shape):
+    if ref is not None and _is_torch(ref):
+        import torch
+        return torch.empty(shape, dtype=torch.float64, device=ref.device)
+    return np.empty(shape, dtype=np.float64)
+
+
+def _dptr(a, c=None):
+    a = a if c is None else a[c]
+    return C.cast(C.c_void_p(a.data_ptr() if _is_torch(a) else a.ctypes.data), L.DP)
+
+
+def _dtable(a):
+    t = (L.DP * max(1, a.shape[0]))()
+    for c in range(a.shape[0]):
+        t[c] = _dptr(a, c)
+    return t
+
+
+def welch_sums(x, ref=None, hop: int = 4096, window="hann", stream=None):
+    """dsp_welch: the raw Welch sums of the rows of x [C, L] (torch CUDA tensor,
+    or numpy on the host) over 8192-point frames of hop `hop`, and with the row
+    ref [L] the reference's and the cross sums.  Returns float64 (sxx [C, 4097],
+    srr [4097] or None, sxy [C, 2 * 4097] interleaved (re, im) or None), where x lives."""
+    in_ptrs, r = _rows(x)
+    C_, L_, K = len(in_ptrs), int(x.shape[1]), 4097
+    sp = _welch_spec(hop, window)
+    sxx = _f64_like(r, (C_, K))
+    srr = sxy = None
+    ref_p = None
+    if ref is not None:
+        ref_ptrs, _ = _rows(ref[None, :] if _is_torch(ref) else np.asarray(ref)[None, :])
+        assert int(ref.shape[0]) == L_, "ref and x must have the same length"
+        ref_p = C.cast(C.c_void_p(ref_ptrs[0]), L.FP)
+        srr, sxy = _f64_like(r, (K,)), _f64_like(r, (C_, 2 * K))
+    ex = _exec(r, 0, stream)
+    check(L.lib().dsp_welch(chan_table(in_ptrs), C_, L_, ref_p, _dtable(sxx), _dptr(srr) if ref is not None else None,
+                            _dtable(sxy) if ref is not None else None, C.byref(sp), C.byref(ex)), "dsp_welch")
+    return sxx, srr, sxy
+
+
+def welch_derive(sxx, srr, sxy, frames: int, sr: float, win_sum: float, win_sumsq: float, scaling: str = "density",
+                 psd: bool = True, cross: bool = True) -> dict:
+    """dsp_welch_derive (host only, float64) on numpy sums: {"psd" [C, K],
+    "H1" [C, K] complex128, "coherence" [C, K]}, the cross entries only with srr and sxy."""
+    if scaling not in ("density", "spectrum"):
+        raise ValueError("scaling: 'density' or 'spectrum'")
+    sxx = np.ascontiguousarray(sxx, np.float64)
+    C_, K = sxx.shape
+    cross = cross and srr is not None
+    out = {}
+    p = np.empty((C_, K)) if psd else None
+    h = np.empty((C_, 2 * K)) if cross else None
+    g = np.empty((C_, K)) if cross else None
+    if cross:
+        srr, sxy = np.ascontiguousarray(srr, np.float64), np.ascontiguousarray(sxy, np.float64)
+    check(L.lib().dsp_welch_derive(_dtable(sxx), _dptr(srr) if cross else None, _dtable(sxy) if cross else None, C_, K,
+                                   frames, sr, win_sum, win_sumsq, L.DSP_WELCH_SPECTRUM if scaling == "spectrum" else 0,
+                                   _dtable(p) if psd else None, _dtable(h) if cross else None,
+                                   _dtable(g) if cross else None), "dsp_welch_derive")
+    if psd:
+        out["psd"] = p
+    if cross:
+        out["H1"] = h.view(np.complex128)
+        out["coherence"] = g
+    return out
+
+
+def _welch_host(x, ref, hop, window):
+    """The sums of a call on the host as numpy, with the plan."""
+    sxx, srr, sxy = welch_sums(x, ref, hop, window)
+    if _is_torch(sxx):
+        sxx, srr, sxy = (None if a is None else a.cpu().numpy() for a in (sxx, srr, sxy))
+    return sxx, srr, sxy, welch_plan(int(x.shape[1]), int(x.shape[0]), ref is not None, hop, window)
+
+
+def _welch_freqs(sr, K=4097):
+    return np.arange(K) * (float(sr) / (2 * (K - 1)))
+
+
+def welch(x, sr: float, hop: int = 4096, window="hann", scaling: str = "density"):
+    """The one-sided average spectrum of the rows of x [C, L]: (freqs [4097],
+    psd [C, 4097]) float64 -- scipy.signal.welch(x, sr, w, 8192, 8192 - hop,
+    detrend=False, scaling=scaling) with w the library's symmetric window."""
+    sxx, _, _, p = _welch_host(x, None, hop, window)
+    d = welch_derive(sxx, None, None, p["frames"], sr, p["win_sum"], p["win_sumsq"], scaling)
+    return _welch_freqs(sr), d["psd"]
+
+
+def csd(ref, x, sr: float, hop: int = 4096, window="hann", scaling: str = "density"):
+    """The one-sided cross-spectrum between the row ref [L] and the rows of x
+    [C, L]: (freqs, pxy [C, 4097] complex128), scipy.signal.csd(ref, x, ...)'s sign and scale."""
+    sxx, srr, sxy, p = _welch_host(x, ref, hop, window)
+    if scaling not in ("density", "spectrum"):
+        raise ValueError("scaling: 'density' or 'spectrum'")
+    # dsp_welch_derive has no pxy output: welch_host.cpp welch_derive's psd rule (the scale and
+    # the one-sided factors), applied to sxy -- keep the two in step
+    den = p["frames"] * (p["win_sum"] ** 2 if scaling == "spectrum" else float(sr) * p["win_sumsq"])
+    g = np.full(sxx.shape[1], 2.0)
+    g[0] = g[-1] = 1.0
+    return _welch_freqs(sr), sxy.view(np.complex128) * (g / den)
+
+
+def transfer(ref, x, sr: float, hop: int = 4096, window="hann"):
+    """The H1 transfer function from the row ref [L] to the rows of x [C, L] and
+    its coherence: (freqs, H1 [C, 4097] complex128, coherence [C, 4097])."""
+    sxx, srr, sxy, p = _welch_host(x, ref, hop, window)
+    d = welch_derive(sxx, srr, sxy, p["frames"], sr, p["win_sum"], p["win_sumsq"], psd=False)
+    return _welch_freqs(sr), d["H1"], d["coherence"]
+
+
 def stft_frames(L_: int, N: int, H: int) -> int:
     return int(L.lib().dsp_stft_frame_count(L_, N, H))
 

@@ -477,6 +477,73 @@ int dsp_sweep(uint32_t sr, const dsp_sweep_spec *spec, float *out, uint64_t coun
 /* order >= 1; *samples = T ln(order) / R sr */
 int dsp_sweep_harmonic_offset(uint32_t sr, const dsp_sweep_spec *spec, uint32_t order, double *samples);
 
+/* Welch spectral estimates: the average spectrum of C rows of L samples and,
+ * with a reference row, the cross-spectrum from which the transfer function
+ * (H1) and the coherence follow -- the noise or programme-material measurement
+ * beside the sweep's (dsp_deconvolve).
+ *
+ * N = 8192 only (any other N: DSP_ERR_UNSUPPORTED).  F = dsp_stft_frame_count(
+ * L, N, H) frames with 1 <= H <= N, frame f over [f H, f H + N): no padding and
+ * no detrend, a tail shorter than a frame is ignored.  w is DSP_WIN_HAMMING or
+ * DSP_WIN_HANN, the symmetric table of dsp_stft_magnitude (not scipy's periodic
+ * default).  With X_{c,f} = DFT_N(w in[c][f H ..)), unnormalised, K = 4097
+ * bins, and R_f the same of the optional row ref (L samples, shared by every
+ * channel as in dsp_deconvolve), the call returns raw sums as float64 rows:
+ *   sxx[c][k]             = sum_f |X_{c,f}[k]|^2           C rows of K
+ *   srr[k]                = sum_f |R_f[k]|^2               one row of K
+ *   sxy[c][2k], [2k + 1]  = sum_f conj(R_f[k]) X_{c,f}[k]  C rows of 2 K, (re, im)
+ * sxy has the sign of scipy.signal.csd(ref, in).  srr and sxy are written only
+ * with a ref and must be NULL exactly when ref is NULL.
+ * Summation order (part of the contract): the frames are cut into runs of `run`
+ * consecutive frames, a constant of the plan; a run is summed in float32 in
+ * frame order, the runs are added in float64 in run order.  No float atomics:
+ * the same bits on every run, and channel c's bits do not depend on C.  When
+ * in[c] holds the same samples as ref, the imaginary parts of sxy[c] are
+ * exactly 0.  Accuracy: per row max_k |S - exact| <= 1.5e-6 max_k exact (for sxy
+ * the scale is sqrt(max sxx max srr)) for finite samples; non-finite samples
+ * give undefined sums.
+ * Method: the frames are walked in chunks; a chunk's windowed transforms go to
+ * a device scratch kept per stream, a second launch sums the runs, a third adds
+ * them onto the output rows.  The scratch holds at most 64 MiB of spectra and
+ * never more than 72 MiB in all, whatever L is.
+ * DSP_ERR_INVALID for C = 0, F = 0 (L < N), H = 0 or H > N, an unknown window,
+ * ex->sample_offset != 0, srr / sxy not matching ref, an output row that is
+ * not 8-byte aligned, or any overlap of an output row with an input row or
+ * another output row (nothing is written).  Host rows with
+ * DSP_EXEC_HOST_BUFFERS.  Channel groups of at most 16 run one after another
+ * over the scratch.  The window and twiddle tables are cached per device: a
+ * stream being captured needs one eager call of the same shape first.
+ * DSP_ERR_NO_DEVICE without a device. */
+typedef struct dsp_welch_spec {
+    uint32_t N;     /* 8192 */
+    uint32_t H;     /* 1 .. N */
+    int32_t window; /* DSP_WIN_HAMMING or DSP_WIN_HANN */
+} dsp_welch_spec;   /* NULL: {8192, 4096, DSP_WIN_HANN} */
+
+/* The plan (host only, no device): frames F, bins K, the run length, the bytes
+ * of device scratch, and win_sum = sum w, win_sumsq = sum w^2 in float64 over
+ * the float table the kernel reads.  Any out pointer may be NULL. */
+int dsp_welch_plan(uint64_t L, uint32_t C, int has_ref, const dsp_welch_spec *spec, uint64_t *frames,
+                   uint32_t *bins, uint32_t *run, uint64_t *scratch_bytes, double *win_sum, double *win_sumsq);
+int dsp_welch(const float *const *in, uint32_t C, uint64_t L, const float *ref /* may be NULL */,
+              double *const *sxx, double *srr, double *const *sxy, const dsp_welch_spec *spec, const dsp_exec *ex);
+
+/* From the sums to the estimates (host only, float64); any output may be NULL,
+ * srr and sxy may be NULL when H1 and coherence are.
+ *   psd[c][k]       = g_k sxx[c][k] / (frames sr win_sumsq), g = 2 except at DC
+ *                     and Nyquist (k = 0, bins - 1): one-sided, scipy's
+ *                     scaling='density'.  DSP_WELCH_SPECTRUM divides by
+ *                     frames win_sum^2 instead (scaling='spectrum').
+ *   H1[c][2k], +1   = sxy[c][k] / srr[k]
+ *   coherence[c][k] = |sxy[c][k]|^2 / (sxx[c][k] srr[k])
+ * A bin whose denominator is 0 gives H1 = 0 and coherence = 0.
+ * DSP_ERR_INVALID for C = 0, bins = 0, frames = 0, unknown flags, a NULL input
+ * an output needs, or (for psd) a scale that is not finite and positive. */
+#define DSP_WELCH_SPECTRUM 0x1u
+int dsp_welch_derive(const double *const *sxx, const double *srr, const double *const *sxy, uint32_t C,
+                     uint32_t bins, uint64_t frames, double sr, double win_sum, double win_sumsq, uint32_t flags,
+                     double *const *psd, double *const *H1, double *const *coherence);
+
 /* Test hooks (not for production use).
  * DSP_DEBUG_BIQUAD_SPIN_LIMIT (set): the sleeps a DSP_PLUGIN_BIQUAD look-back
  *   waits for a preceding tile's words before it gives up (value ~0 restores
