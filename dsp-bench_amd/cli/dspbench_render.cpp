@@ -85,6 +85,18 @@
 //                       [{peak_hz, peak_db, power_db}]}}.  A render shorter than
 //                       one frame is an error.  Not with --deconvolve, --loop or
 //                       the multi-GPU modes
+//     --decay OUT.csv   with --deconvolve: the room-acoustic figures of the impulse
+//                       response that run writes (dsp_decay, dsp_decay_derive;
+//                       its negative-time samples fall before the onset): a
+//                       header line, then per channel and band the mid
+//                       frequency in Hz, EDT, T20, T30 in seconds, C50, C80 in
+//                       dB, D50, Ts in ms and the INR in dB; a value that is not
+//                       valid is an empty cell.  Prints one JSON line {"decay":
+//                       {n, hop, bands, fraction, channels: [{onset,
+//                       peak_dbfs}]}}.  Not with --plugin, --convolve, --loop,
+//                       --stft, --psd, --transfer, --rate or the multi-GPU modes
+//     --decay-bands octave|third   31.6 Hz..16 kHz octaves (default) or 25 Hz..
+//                       20 kHz third-octaves, without the bands above rate / 2
 //     --loop NBLOCKS    loop mode (audio.cpp:100-132): NBLOCKS blocks from a
 //                       file that wraps around (no --stft)
 //   multi-GPU (cfg 5, shard.h): one process per GPU, channels sharded one
@@ -114,8 +126,12 @@
 //   min_coherence, gain_db}]}}.  Nothing is resampled or aligned: files of
 //   different rates or lengths, or shorter than one frame, are refused.
 //
+// dspbench_render IR.wav --decay OUT.csv [--decay-bands octave|third]
+//   the same analysis of an impulse response that is already a file: the CSV
+//   and the JSON line of --decay above.
+//
 // options.cpp reads the command line, device.hpp owns what lives on the device,
-// wavio.cpp is the one WAV loader and the one writer; here are the four modes.
+// wavio.cpp is the one WAV loader and the one writer; here are the five modes.
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -222,6 +238,76 @@ int load_input(const Options &o, Device &dev, Wav &in) {
     }, dev, in);
 }
 
+// ---- --decay: ISO 3382 figures of device rows (impulse responses) -----------
+int write_decay(const Options &o, float *const *rows, uint32_t C, uint64_t L, uint32_t rate, Device &dev) {
+    dsp_decay_spec sp = o.decay_bands == "third" ? dsp_decay_spec{3u, -16, 13} : dsp_decay_spec{1u, -5, 4};
+    // without the bands whose upper edge lies above rate / 2
+    while (sp.k_hi > sp.k_lo && 1000.0 * std::pow(10.0, 0.3 * (sp.k_hi + 0.5) / sp.fraction) > 0.5 * rate) --sp.k_hi;
+    uint32_t n = 0, hop = 0, B = 0;
+    uint64_t hops = 0;
+    double fm[32];
+    int st = dsp_decay_plan(L, C, rate, &sp, &n, nullptr, &hop, &B, &hops, nullptr, fm);
+    if (st) return fail("dsp_decay_plan", st);
+    const size_t R = (size_t)C * B, row = hops;
+    DevBuf buf;  // [2][R][hops] float64, then the onsets and the peaks
+    HIPCK(hipMalloc(&buf.h, 2 * R * row * sizeof(double) + C * (sizeof(uint64_t) + sizeof(float))));
+    double *de = (double *)buf.h, *dm = de + R * row;
+    uint64_t *donset = (uint64_t *)(dm + R * row);
+    float *dpeak = (float *)(donset + C);
+    std::vector<double *> pe(R), pm(R);
+    for (size_t r = 0; r < R; ++r) pe[r] = de + r * row, pm[r] = dm + r * row;
+    if ((st = dsp_decay(rows, C, L, rate, &sp, dpeak, donset, pe.data(), pm.data(), &dev.ex))) return fail("dsp_decay", st);
+    std::vector<double> h(2 * R * row);
+    std::vector<uint64_t> onset(C);
+    std::vector<float> peak(C);
+    HIPCK(hipMemcpyAsync(h.data(), de, h.size() * sizeof(double), hipMemcpyDeviceToHost, dev.stream.h));
+    HIPCK(hipMemcpyAsync(onset.data(), donset, C * sizeof(uint64_t), hipMemcpyDeviceToHost, dev.stream.h));
+    HIPCK(hipMemcpyAsync(peak.data(), dpeak, C * sizeof(float), hipMemcpyDeviceToHost, dev.stream.h));
+    HIPCK(hipStreamSynchronize(dev.stream.h));
+    std::string csv = "channel,fm_hz,edt_s,t20_s,t30_s,c50_db,c80_db,d50,ts_ms,inr_db\n";
+    std::string j = "{\"decay\": {\"n\": " + std::to_string(n) + ", \"hop\": " + std::to_string(hop) + ", \"bands\": " +
+                    std::to_string(B) + ", \"fraction\": " + std::to_string(sp.fraction) + ", \"channels\": [";
+    char b[48];
+    for (uint32_t c = 0; c < C; ++c) {
+        j += std::string(c ? ", " : "") + "{\"onset\": " + std::to_string(onset[c]) + ", \"peak_dbfs\": " +
+             json_num(20.0 * std::log10((double)peak[c])) + "}";
+        for (uint32_t k = 0; k < B; ++k) {
+            const size_t r = (size_t)c * B + k;
+            dsp_decay_result res;
+            if ((st = dsp_decay_derive(&h[r * row], &h[(R + r) * row], L, onset[c], hop, rate, &res)))
+                return fail("dsp_decay_derive", st);
+            std::snprintf(b, sizeof b, "%u,%.9g", c, fm[k]);
+            csv += b;
+            const double v[8] = {res.edt, res.t20, res.t30, res.c50, res.c80, res.d50, 1e3 * res.ts, res.inr};
+            for (double x : v) {
+                if (std::isnan(x)) b[0] = ',', b[1] = 0;  // not valid: an empty cell
+                else std::snprintf(b, sizeof b, ",%.9g", x);
+                csv += b;
+            }
+            csv += "\n";
+        }
+    }
+    if (int e = write_file(o.decay_path.c_str(), {{csv.data(), csv.size()}})) return e;
+    std::printf("%s]}}\n", j.c_str());
+    return 0;
+}
+
+// ---- IR.wav --decay OUT.csv: the analysis of a file ---------------------------
+int run_decay(const Options &o) {
+    Device dev(o.device);
+    Wav in;
+    if (int e = load_input(o, dev, in)) return e;
+    if (in.info.frames == 0) {
+        std::fprintf(stderr, "dspbench_render: --decay: %s is empty\n", o.in_path.c_str());
+        return 1;
+    }
+    if (int e = write_decay(o, in.rows.ptr.data(), in.info.channels, in.info.frames, in.info.sample_rate, dev)) return e;
+    std::printf("dspbench_render: %s: %u ch x %llu frames @ %u Hz, decay analysis -> %s, %.1f ms end to end\n",
+                o.in_path.c_str(), in.info.channels, (unsigned long long)in.info.frames, in.info.sample_rate,
+                o.decay_path.c_str(), dev.ms());
+    return 0;
+}
+
 // ---- --deconvolve: the recording deconvolved by REF's first channel ---------
 int run_deconvolve(const Options &o) {
     Device dev(o.device);
@@ -274,6 +360,8 @@ int run_deconvolve(const Options &o) {
     }
     std::printf("%s]}\n", j.c_str());
     if (int e = write_file(o.out_path.c_str(), {{w.bytes.data(), w.size}})) return e;
+    if (!o.decay_path.empty())  // of the rows the file holds (before its sample format)
+        if (int e = write_decay(o, ir.ptr.data(), Cf, irl, rate, dev)) return e;
     std::printf("dspbench_render: %s deconvolved by %s: %u ch x %llu frames @ %u Hz -> %s (n = %u), %.1f ms end to end\n",
                 o.in_path.c_str(), ref_path, Cf, (unsigned long long)irl, rate, o.out_path.c_str(), n, dev.ms());
     return 0;
@@ -768,6 +856,7 @@ int main(int argc, char **argv) {
     case Options::SWEEP: return run_sweep(p.opt);
     case Options::DECONVOLVE: return run_deconvolve(p.opt);
     case Options::TRANSFER: return run_transfer(p.opt);
+    case Options::DECAY: return run_decay(p.opt);
     default: return run_render(p.opt, started);
     }
 }

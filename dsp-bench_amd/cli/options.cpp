@@ -45,6 +45,8 @@ const struct {
     {"--ir-length", true, u64_nonzero<&O::ir_length>},
     {"--psd", true, text<&O::psd_path>},
     {"--transfer", true, text<&O::transfer_path>},
+    {"--decay", true, text<&O::decay_path>},
+    {"--decay-bands", true, given<text<&O::decay_bands>, &O::have_decay_bands>},
     {"--gain", true, f32<&O::gain>},
     {"--ir", true, ir_pair},
     {"--block", true, u32<&O::block>},
@@ -92,6 +94,23 @@ const struct {
      "--loudness, --normalize and the multi-GPU modes\n", true},
     {[](const O &o) { return !o.psd_path.empty() && (!o.deconv_path.empty() || o.loop_blocks || o.multi_gpu()); },
      "dspbench_render: --psd excludes --deconvolve, --loop and the multi-GPU modes\n", true},
+    {[](const O &o) { return o.have_decay_bands && o.decay_bands != "octave" && o.decay_bands != "third"; }, nullptr, true},
+    {[](const O &o) { return o.have_decay_bands && o.decay_path.empty(); },
+     "dspbench_render: --decay-bands needs --decay\n", true},
+    {[](const O &o) {
+         return !o.decay_path.empty() &&
+                (o.have_plugin || !o.conv_path.empty() || o.loop_blocks || o.multi_gpu() || o.rate ||
+                 !o.stft_path.empty() || !o.psd_path.empty() || !o.transfer_path.empty());
+     },
+     "dspbench_render: --decay excludes --plugin, --convolve, --loop, --stft, --psd, --transfer, --rate and the "
+     "multi-GPU modes\n", true},
+    {[](const O &o) { return !o.decay_path.empty() && !o.decay_alone && o.deconv_path.empty(); },
+     "dspbench_render: --decay goes with --deconvolve, or stands alone: IR.wav --decay OUT.csv\n", true},
+    {[](const O &o) {
+         return o.decay_alone && (o.decay_path.empty() || !o.deconv_path.empty() || o.levels() || !o.bits.empty() ||
+                                  o.dev_channels || o.dev_rate);
+     },
+     "dspbench_render: IR.wav --decay OUT.csv takes only --decay-bands and --device\n", true},
     {[](const O &o) { return o.rate && (o.dev_rate || o.loop_blocks || o.multi_gpu()); },
      "dspbench_render: --rate excludes --device-rate, --loop and the multi-GPU modes\n", true},
     {[](const O &o) { return o.levels() && (o.loop_blocks || o.multi_gpu()); },
@@ -142,9 +161,10 @@ const char *usage_text() {
            "       [--loudness] [--normalize LUFS [--true-peak-ceiling DBTP [--limit]]]\n"
            "       [--limit-lookahead MS] [--limit-release MS]\n"
            "       [--deconvolve REF.wav [--deconv-eps E] [--deconv-pre N] [--ir-length N]]\n"
-           "       [--psd OUT.csv]\n"
+           "       [--psd OUT.csv] [--decay OUT.csv [--decay-bands octave|third]]\n"
            "       [--world W --rank R --comm-id FILE [--run-id STR] [--chunk SAMPLES]]\n"
            "       dspbench_render REC.wav OUT.csv --transfer REF.wav [--device N]\n"
+           "       dspbench_render IR.wav --decay OUT.csv [--decay-bands octave|third] [--device N]\n"
            "       dspbench_render --sweep F1:F2:SECONDS[:RATE[:BITS]] OUT.wav\n";
 }
 
@@ -157,10 +177,12 @@ Parsed parse_options(int argc, const char *const *argv, const Env &env) {
     if (argc < 3) return usage_error();
     Parsed p;
     Options &o = p.opt;
-    o.in_path = argv[1], o.out_path = argv[2];
+    o.in_path = argv[1];
+    o.decay_alone = std::string(argv[2]) == "--decay";  // IR.wav --decay OUT.csv: one positional argument
+    if (!o.decay_alone) o.out_path = argv[2];
     if (env.dspb_run_id) o.run_id = env.dspb_run_id;
     else if (env.torchelastic_run_id) o.run_id = env.torchelastic_run_id;
-    for (int i = 3; i < argc; ++i) {
+    for (int i = o.decay_alone ? 2 : 3; i < argc; ++i) {
         const auto *opt = std::begin(kOptions);
         while (opt != std::end(kOptions) && argv[i] != std::string(opt->name)) ++opt;
         // (a name that is not an option and one whose value is missing are both the usage text)
@@ -168,6 +190,7 @@ Parsed parse_options(int argc, const char *const *argv, const Env &env) {
     }
     if (!o.deconv_path.empty()) o.mode = Options::DECONVOLVE;
     else if (!o.transfer_path.empty()) o.mode = Options::TRANSFER;
+    else if (o.decay_alone) o.mode = Options::DECAY;
     if (o.multi()) {  // torchrun-style environment when not given explicitly
         if (!o.world) o.world = env.world_size ? (uint32_t)std::atoi(env.world_size) : 1;
         if (!o.have_rank) o.rank = env.rank ? (uint32_t)std::atoi(env.rank) : 0;

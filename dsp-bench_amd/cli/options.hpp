@@ -7,10 +7,13 @@
 #include <string>
 
 struct Options {
-    enum Mode { RENDER, DECONVOLVE, SWEEP, TRANSFER } mode = RENDER;
+    enum Mode { RENDER, DECONVOLVE, SWEEP, TRANSFER, DECAY } mode = RENDER;
     std::string in_path, out_path;
     std::string plugin = "gain_test", conv_path, deconv_path, stft_path, bits, comm_path, run_id;
     std::string psd_path, transfer_path;  // --psd OUT.csv (of the render); REC.wav OUT.csv --transfer REF.wav
+    // --decay OUT.csv [--decay-bands octave|third]: of --deconvolve's impulse response, or IR.wav --decay OUT.csv
+    std::string decay_path, decay_bands = "octave";
+    bool have_decay_bands = false, decay_alone = false;
     bool have_plugin = false, have_rank = false;
     bool loudness = false, normalize = false, ceiling = false, limit = false;
     float gain = -1.f, ir_gain = 0.9f, ir_step = 0.002f;

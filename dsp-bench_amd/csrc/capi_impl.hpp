@@ -208,7 +208,7 @@ enum ScratchSlot : int {
     kScratchConv = 2,        // a CONV channel group's spectra
     kScratchLoudness = 3,    // a dsp_loudness channel group's partial sums, hop energies and peaks
     kScratchLimiter = 4,     // a dsp_limiter call's hold rows, tile aggregates, carries and result words
-    kScratchBigFft = 5,      // a dsp_rfft / dsp_irfft / dsp_deconvolve channel group's work buffers and spectra
+    kScratchBigFft = 5,      // a dsp_rfft / dsp_irfft / dsp_deconvolve / dsp_decay group's work buffers, spectra and rows
     kScratchSpectrumHop = 6, // the hop the one-frame launch of a spectrum-row miss renders beside its row
     kScratchWelch = 7,       // a dsp_welch channel group's chunk of spectra and its runs' partial sums
 };

@@ -1,11 +1,12 @@
 // capi_signal.cpp -- the Plugin-free row calls of the C ABI
 // (include/dspbench/dspbench.h): dsp_resample, dsp_loudness, dsp_limiter,
-// dsp_rfft / dsp_irfft, dsp_deconvolve, dsp_sweep and dsp_welch, with their
-// plans.  Each checks its arguments and its rows' layout before it looks at a
+// dsp_rfft / dsp_irfft, dsp_deconvolve, dsp_sweep, dsp_welch and dsp_decay, with
+// their plans.  Each checks its arguments and its rows' layout before it looks at a
 // device, holds its cached tables until its launches are enqueued, and walks
 // its channels in groups of kMaxChannels.  What it shares with capi.cpp and
 // capi_render.cpp is in capi_impl.hpp.
 #include "capi_impl.hpp"
+#include "decay_host.hpp"
 #include "limiter_host.hpp"
 #include "loudness_host.hpp"
 #include "sweep_host.hpp"
@@ -99,16 +100,24 @@ static int welch_plan_checked(uint64_t L, uint32_t C, int has_ref, const dsp_wel
     return plan_status(r, why);
 }
 
-// dsp_welch's float64 output rows: none NULL, each 8-byte aligned; *out = the rows as float rows
-static int welch_double_rows(const char *name, double *const *rows, uint32_t C, std::vector<const float *> *out) {
+// float64 output rows (dsp_welch, dsp_decay): none NULL, each 8-byte aligned; *out = the rows as float rows
+static int double_rows(const char *call, const char *name, double *const *rows, uint32_t C,
+                       std::vector<const float *> *out) {
     if (!rows) return invalid("%s is NULL", name);
     out->resize(C);
     for (uint32_t c = 0; c < C; ++c) {
         if (!rows[c]) return invalid("%s[%u] is NULL", name, c);
-        if (!aligned(rows[c], 8)) return invalid("dsp_welch: %s[%u] is not 8-byte aligned", name, c);
+        if (!aligned(rows[c], 8)) return invalid("%s: %s[%u] is not 8-byte aligned", call, name, c);
         (*out)[c] = reinterpret_cast<const float *>(rows[c]);
     }
     return DSP_OK;
+}
+
+static_assert(kDecayGroup == kMaxChannels, "decay_plan sizes the scratch for launches of kMaxChannels rows");
+static int decay_plan_checked(uint64_t L, uint32_t C, uint32_t sr, const dsp_decay_spec *spec, DecayPlan *p) {
+    const char *why = nullptr;
+    const int r = decay_plan(L, C, sr, spec, p, &why);
+    return plan_status(r, why);
 }
 
 // A call's large-FFT context (fft_big.hip): the hold on n's cached twiddle
@@ -684,7 +693,7 @@ int dsp_welch(const float *const *in, uint32_t C, uint64_t L, const float *ref, 
     if ((st = check_rows("in", in, C))) return st;
     // the float64 rows as float rows of twice the length, for the layout checks
     std::vector<const float *> fxx, fxy;
-    if ((st = welch_double_rows("sxx", sxx, C, &fxx)) || (ref && (st = welch_double_rows("sxy", sxy, C, &fxy)))) return st;
+    if ((st = double_rows("dsp_welch", "sxx", sxx, C, &fxx)) || (ref && (st = double_rows("dsp_welch", "sxy", sxy, C, &fxy)))) return st;
     const float *frr = reinterpret_cast<const float *>(srr);
     if (ref && !aligned(srr, 8)) return invalid("dsp_welch: srr is not 8-byte aligned");
     {
@@ -764,6 +773,123 @@ int dsp_welch_derive(const double *const *sxx, const double *srr, const double *
             return invalid("dsp_welch_derive: the scale (sr, win_sum, win_sumsq) must be finite and positive");
     }
     welch_derive(sxx, srr, sxy, C, bins, frames, sr, win_sum, win_sumsq, flags, psd, H1, coherence);
+    return DSP_OK;
+}
+
+int dsp_decay_plan(uint64_t L, uint32_t C, uint32_t sr, const dsp_decay_spec *spec, uint32_t *n, uint32_t *P,
+                   uint32_t *hop, uint32_t *bands, uint64_t *hops, uint64_t *scratch_bytes, double *fm) {
+    DecayPlan p;
+    if (int st = decay_plan_checked(L, C, sr, spec, &p)) return st;
+    if (n) *n = p.n;
+    if (P) *P = p.P;
+    if (hop) *hop = p.hop;
+    if (bands) *bands = p.bands;
+    if (hops) *hops = p.hops;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    if (fm) std::memcpy(fm, p.fm, sizeof p.fm);
+    return DSP_OK;
+}
+
+int dsp_decay(const float *const *in, uint32_t C, uint64_t L, uint32_t sr, const dsp_decay_spec *spec, float *peak,
+              uint64_t *onset, double *const *energy, double *const *moment, const dsp_exec *ex) {
+    DecayPlan p;
+    int st;
+    if ((st = decay_plan_checked(L, C, sr, spec, &p))) return st;
+    if ((st = whole_rows_only(ex, "dsp_decay"))) return st;
+    if ((st = check_rows("in", in, C))) return st;
+    if (!peak || !onset) return invalid("dsp_decay: peak or onset is NULL");
+    if (!aligned(peak, 4) || !aligned(onset, 8)) return invalid("dsp_decay: peak or onset is misaligned");
+    const uint32_t B = p.bands, R = C * B;
+    if (R / B != C) return invalid("dsp_decay: too many rows");
+    // the float64 rows as float rows of twice the length, for the layout checks
+    std::vector<const float *> fe, fm;
+    if ((st = double_rows("dsp_decay", "energy", energy, R, &fe)) || (moment && (st = double_rows("dsp_decay", "moment", moment, R, &fm))))
+        return st;
+    {
+        const float *fp = peak, *fo = reinterpret_cast<const float *>(onset);
+        const Rows I{in, C, L}, E{fe.data(), R, 2 * p.hops}, M{fm.data(), moment ? R : 0u, 2 * p.hops}, Pk{&fp, 1, C},
+            On{&fo, 1, 2ull * C};
+        const Rows *outs[] = {&E, &M, &Pk, &On};
+        bool bad = rows_overlap_each_other(E) || rows_overlap_each_other(M);
+        for (int i = 0; i < 4; ++i) {
+            bad = bad || rows_overlap(I, *outs[i]);
+            for (int j = i + 1; j < 4; ++j) bad = bad || rows_overlap(*outs[i], *outs[j]);
+        }
+        if (bad) return invalid("dsp_decay: an output row overlaps an input row or another output row");
+    }
+    DeviceGuard g(ex);
+    if (g.status) return g.status;
+    hipStream_t s = stream_of(ex);
+    Stage stage(ex);
+    const std::vector<const float *> din = stage.in_rows(in, C, L);
+    float *dpeak = (float *)stage.out_bytes(peak, sizeof(float) * C);
+    unsigned long long *donset = (unsigned long long *)stage.out_bytes(onset, sizeof(uint64_t) * C);
+    std::vector<double *> de(R), dm(R, nullptr);
+    for (uint32_t r = 0; r < R; ++r) {
+        de[r] = (double *)stage.out_bytes(energy[r], sizeof(double) * p.hops);
+        if (moment) dm[r] = (double *)stage.out_bytes(moment[r], sizeof(double) * p.hops);
+    }
+    if (stage.status) return stage.status;
+    BigFft f;
+    if ((st = big_fft_open(p.n, p.scratch_bytes, g.dev, s, &f))) return st;
+    char *base = reinterpret_cast<char *>(f.work);
+    const uint32_t bins = p.n / 2 + 1;
+    v2f *X = reinterpret_cast<v2f *>(base + p.off_x), *Y = reinterpret_cast<v2f *>(base + p.off_y);
+    float *ir = reinterpret_cast<float *>(base + p.off_ir);
+
+    // peak and onset of every channel, straight onto the output words
+    st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
+        DecayArgs A{};
+        group_rows(din, c0, cn, &A.in, 4);
+        A.cn = cn;
+        A.L = L;
+        A.peak = dpeak + c0;
+        A.onset = donset + c0;
+        return launch_decay_onset(A, s);
+    });
+    if (st) return st;
+    // p.rows channels at a time: their spectra, then their (channel, band) rows in groups of p.rows
+    for (uint32_t c0 = 0; c0 < C; c0 += p.rows) {
+        const uint32_t cc = std::min(C - c0, p.rows);
+        {
+            BigFftArgs A{};
+            if ((st = big_fft_args(f, cc, &A))) return st;
+            A.L = L;
+            A.in_aligned8 = group_rows(din, c0, cc, &A.in, 8);
+            for (uint32_t j = 0; j < cc; ++j) A.out.p[j] = reinterpret_cast<float *>(X + (uint64_t)j * bins);
+            if ((st = launch_big_rfft(A, s))) return st;
+        }
+        for (uint32_t q0 = 0; q0 < cc * B; q0 += p.rows) {
+            const uint32_t nr = std::min(cc * B - q0, p.rows);
+            DecayArgs D{};
+            BigFftArgs A{};
+            if ((st = big_fft_args(f, nr, &A))) return st;
+            A.Lout = L;
+            D.L = L, D.nrows = nr, D.bins = bins, D.X = X, D.Y = Y, D.Qd = (float)p.Qd;
+            D.onset = donset, D.ir = ir, D.Lp = p.Lp, D.hop = p.hop, D.hops = p.hops;
+            D.pre = reinterpret_cast<double *>(base + p.off_pre);
+            for (uint32_t r = 0; r < nr; ++r) {
+                const uint32_t j = (q0 + r) / B, b = (q0 + r) % B, row = (c0 + j) * B + b;
+                D.xrow[r] = j;
+                D.chan[r] = c0 + j;
+                D.fscale[r] = (float)((double)sr / ((double)p.n * p.fm[b]));
+                D.energy[r] = de[row];
+                D.moment[r] = dm[row];
+                A.in.p[r] = reinterpret_cast<const float *>(Y + (uint64_t)r * bins);
+                A.out.p[r] = ir + (uint64_t)r * p.Lp;
+            }
+            if ((st = launch_decay_mask(D, s)) || (st = launch_big_irfft(A, s)) || (st = launch_decay_hops(D, s))) return st;
+        }
+    }
+    return (st = stage.copy_back()) ? st : finish(ex);
+}
+
+int dsp_decay_derive(const double *energy, const double *moment, uint64_t L, uint64_t onset, uint32_t hop, uint32_t sr,
+                     dsp_decay_result *res) {
+    if (!energy || !res) return invalid("dsp_decay_derive: energy or res is NULL");
+    if (hop == 0 || hop != decay_hop(sr)) return invalid("dsp_decay_derive: hop is not dsp_decay_plan's for this rate");
+    if (onset > L) return invalid("dsp_decay_derive: onset > L");
+    decay_derive(energy + 1, moment ? moment + 1 : nullptr, (L - onset) / hop, hop, sr, res);
     return DSP_OK;
 }
 

@@ -285,6 +285,34 @@ struct WelchArgs {
     uint32_t first;        // the call's first chunk: the sums start from zero
 };
 int launch_welch_chunk(const WelchArgs &A, hipStream_t s);
+// dsp_decay (decay.hip): peak and onset of a channel group; the band masks of
+// a group of (channel, band) rows; the rows' hop sums (decay_host.hpp has the
+// scratch layout)
+struct DecayArgs {
+    ChanIn in;                  // onset: cn unfiltered rows
+    uint32_t cn;
+    uint64_t L;
+    float *peak;                // onset: the group's first channel
+    unsigned long long *onset;  // onset: the group's first channel; hops: the call's channel 0
+    uint32_t nrows;             // mask, hops: rows of this group
+    uint32_t bins;              // n / 2 + 1
+    const v2f *X;               // channel spectra, [..][bins]
+    v2f *Y;                     // [nrows][bins] band spectra
+    uint32_t xrow[kMaxChannels];   // a row's spectrum in X
+    uint32_t chan[kMaxChannels];   // a row's channel of the call
+    float fscale[kMaxChannels];    // sr / (n fm): bin k lies at f / fm = k fscale
+    float Qd;
+    const float *ir;            // [nrows][Lp] band-filtered rows
+    uint64_t Lp;
+    double *energy[kMaxChannels];  // output rows of `hops`
+    double *moment[kMaxChannels];  // or NULL
+    double *pre;                // [nrows][2][hops] sums of the pieces before the onset: energy, moment
+    uint32_t hop;
+    uint64_t hops;
+};
+int launch_decay_onset(const DecayArgs &A, hipStream_t s);
+int launch_decay_mask(const DecayArgs &A, hipStream_t s);
+int launch_decay_hops(const DecayArgs &A, hipStream_t s);
 int launch_minmax(const float *x, uint64_t n, uint32_t P, float *vmax, float *vmin, hipStream_t s);
 int launch_spectro(const float *mag, uint64_t F, uint32_t K, uint64_t ld, uint32_t P, float *out,
                    hipStream_t s);

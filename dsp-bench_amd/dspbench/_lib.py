@@ -103,6 +103,23 @@ class dsp_welch_spec(C.Structure):
 
 DSP_WELCH_SPECTRUM = 0x1
 
+
+class dsp_decay_spec(C.Structure):
+    _fields_ = [("fraction", C.c_uint32), ("k_lo", C.c_int32), ("k_hi", C.c_int32)]
+
+
+class dsp_decay_result(C.Structure):
+    _fields_ = [("edt", C.c_double), ("t20", C.c_double), ("t30", C.c_double), ("c50", C.c_double),
+                ("c80", C.c_double), ("d50", C.c_double), ("ts", C.c_double), ("inr", C.c_double),
+                ("flags", C.c_uint32), ("truncation", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+DSP_DECAY_SILENT = 0x1
+DSP_DECAY_EDT_INVALID = 0x2
+DSP_DECAY_T20_INVALID = 0x4
+DSP_DECAY_T30_INVALID = 0x8
+DSP_DECAY_SHORT = 0x10
+
 DPP = C.POINTER(C.POINTER(C.c_double))
 DP = C.POINTER(C.c_double)
 
@@ -220,6 +237,13 @@ _SIGS = {
                             C.POINTER(dsp_exec)]),
     "dsp_welch_derive": (C.c_int, [DPP, DP, DPP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_double, C.c_double,
                                    C.c_double, C.c_uint32, DPP, DPP, DPP]),
+    "dsp_decay_plan": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(dsp_decay_spec), C.POINTER(C.c_uint32),
+                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), DP]),
+    "dsp_decay": (C.c_int, [FPP, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(dsp_decay_spec), FP,
+                            C.POINTER(C.c_uint64), DPP, DPP, C.POINTER(dsp_exec)]),
+    "dsp_decay_derive": (C.c_int, [DP, DP, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                   C.POINTER(dsp_decay_result)]),
     "dsp_render_offline": (C.c_int, [FPP, C.c_uint32, C.c_uint64, FPP, C.c_uint32, C.c_uint32,
                                      C.c_float, C.POINTER(dsp_plugin), C.POINTER(dsp_exec)]),
     "dsp_render_loop": (C.c_int, [FPP, C.c_uint32, C.c_uint64, C.c_uint64, FPP, C.c_uint32, C.c_uint32,

@@ -560,6 +560,98 @@ def transfer(ref, x, sr: float, hop: int = 4096, window="hann"):
     return _welch_freqs(sr), d["H1"], d["coherence"]
 
 
+_DECAY_BANDS = {"octave": (1, -5, 4), "third": (3, -16, 13)}
+_DECAY_FIELDS = ("edt", "t20", "t30", "c50", "c80", "d50", "ts", "inr")
+
+
+def decay_plan(L_: int, sr: int, fraction: int = 1, k_lo: int = -5, k_hi: int = 4, channels: int = 1) -> dict:
+    """dsp_decay_plan (host only): the transform size n, the padding P, hop, the
+    band count, the length `hops` of an energy row, the device scratch bytes and
+    the bands' mid frequencies fm."""
+    sp = L.dsp_decay_spec(fraction, k_lo, k_hi)
+    n, P, hop, bands, hops, sb = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+    fm = (C.c_double * 32)()
+    check(L.lib().dsp_decay_plan(L_, channels, sr, C.byref(sp), C.byref(n), C.byref(P), C.byref(hop), C.byref(bands),
+                                 C.byref(hops), C.byref(sb), fm), "dsp_decay_plan")
+    return {"n": n.value, "P": P.value, "hop": hop.value, "bands": bands.value, "hops": hops.value,
+            "scratch_bytes": sb.value, "fm": np.array(fm[:bands.value])}
+
+
+def decay_energies(x, sr: int, fraction: int = 1, k_lo: int = -5, k_hi: int = 4, moments: bool = True, stream=None):
+    """dsp_decay: the hop energies of the band-filtered rows of x [C, L] (torch
+    CUDA tensor, or numpy on the host).  Returns (peak [C] float32, onset [C]
+    uint64 (int64 on torch), energy [C, bands, hops] float64, moment likewise or
+    None), where x lives."""
+    in_ptrs, r = _rows(x)
+    C_, L_ = len(in_ptrs), int(x.shape[1])
+    p = decay_plan(L_, sr, fraction, k_lo, k_hi, C_)
+    B, hops = p["bands"], p["hops"]
+    sp = L.dsp_decay_spec(fraction, k_lo, k_hi)
+    energy = _f64_like(r, (C_ * B, hops))
+    moment = _f64_like(r, (C_ * B, hops)) if moments else None
+    if _is_torch(r):
+        import torch
+        peak = torch.empty((C_,), dtype=torch.float32, device=r.device)
+        onset = torch.empty((C_,), dtype=torch.int64, device=r.device)
+        pp, po = peak.data_ptr(), onset.data_ptr()
+    else:
+        peak, onset = np.empty(C_, np.float32), np.empty(C_, np.uint64)
+        pp, po = peak.ctypes.data, onset.ctypes.data
+    ex = _exec(r, 0, stream)
+    check(L.lib().dsp_decay(chan_table(in_ptrs), C_, L_, sr, C.byref(sp), C.cast(C.c_void_p(pp), L.FP),
+                            C.cast(C.c_void_p(po), C.POINTER(C.c_uint64)), _dtable(energy),
+                            _dtable(moment) if moments else None, C.byref(ex)), "dsp_decay")
+    shape = (C_, B, hops)
+    return peak, onset, energy.reshape(shape), (moment.reshape(shape) if moments else None)
+
+
+def decay_derive(energy, moment, L_: int, onset: int, hop: int, sr: int) -> dict:
+    """dsp_decay_derive (host only, float64) on one energy row (and its moment
+    row, or None): edt, t20, t30, c50, c80, d50, ts, inr, flags, truncation."""
+    e = np.ascontiguousarray(energy, np.float64)
+    m = None if moment is None else np.ascontiguousarray(moment, np.float64)
+    assert e.ndim == 1 and e.shape[0] == (L_ + hop - 1) // hop + 1 and (m is None or m.shape == e.shape)
+    res = L.dsp_decay_result()
+    check(L.lib().dsp_decay_derive(_dptr(e), None if m is None else _dptr(m), L_, int(onset), hop, sr, C.byref(res)),
+          "dsp_decay_derive")
+    out = {k: getattr(res, k) for k in _DECAY_FIELDS}
+    out["flags"], out["truncation"] = res.flags, res.truncation
+    return out
+
+
+def decay(ir, sr: int, bands="octave") -> dict:
+    """The ISO 3382 figures of the impulse responses ir [C, L] per band: a dict of
+    float64 arrays [C, bands] (edt, t20, t30 in seconds, c50, c80 in dB, d50, ts
+    in seconds, inr in dB; NaN where not derivable) and flags [C, bands], plus fm
+    [bands] in Hz, onset [C], peak [C] and hop.  bands: 'octave' (31.6 Hz..16 kHz),
+    'third' (25 Hz..20 kHz), each without the bands whose upper edge lies above
+    sr / 2, or (fraction, k_lo, k_hi) as given."""
+    if isinstance(bands, str):
+        if bands not in _DECAY_BANDS:
+            raise ValueError(f"bands {bands!r}: 'octave', 'third' or (fraction, k_lo, k_hi)")
+        fraction, k_lo, k_hi = _DECAY_BANDS[bands]
+        while k_hi > k_lo and 1000.0 * 10.0 ** (0.3 * (k_hi + 0.5) / fraction) > 0.5 * sr:
+            k_hi -= 1
+    else:
+        fraction, k_lo, k_hi = bands
+    L_ = int(ir.shape[1])
+    p = decay_plan(L_, sr, fraction, k_lo, k_hi, int(ir.shape[0]))
+    peak, onset, energy, moment = decay_energies(ir, sr, fraction, k_lo, k_hi)
+    if _is_torch(energy):
+        peak, onset, energy, moment = (a.cpu().numpy() for a in (peak, onset, energy, moment))
+    C_, B = energy.shape[:2]
+    out = {k: np.empty((C_, B)) for k in _DECAY_FIELDS}
+    out["flags"] = np.zeros((C_, B), np.uint32)
+    for c in range(C_):
+        for b in range(B):
+            d = decay_derive(energy[c, b], moment[c, b], L_, int(onset[c]), p["hop"], sr)
+            for k in _DECAY_FIELDS:
+                out[k][c, b] = d[k]
+            out["flags"][c, b] = d["flags"]
+    out["fm"], out["onset"], out["peak"], out["hop"] = p["fm"], onset.astype(np.uint64), peak, p["hop"]
+    return out
+
+
 def stft_frames(L_: int, N: int, H: int) -> int:
     return int(L.lib().dsp_stft_frame_count(L_, N, H))
 

@@ -544,6 +544,117 @@ int dsp_welch_derive(const double *const *sxx, const double *srr, const double *
                      uint32_t bins, uint64_t frames, double sr, double win_sum, double win_sumsq, uint32_t flags,
                      double *const *psd, double *const *H1, double *const *coherence);
 
+/* Room-acoustic decay analysis (ISO 3382) of C impulse responses of L samples:
+ * what an impulse response (dsp_deconvolve) is measured for.  dsp_decay returns
+ * per (channel, band) the energy of the band-filtered response in short hops
+ * from the channel's onset, as raw float64 sums; dsp_decay_derive (host only)
+ * turns one such row into reverberation times, clarity, definition and centre
+ * time.
+ *
+ * Bands.  G = 10^0.3, fraction b = 1 (octave) or 3 (third-octave), band index k
+ * has the mid frequency fm = 1000 G^(k / b) Hz.  The spec names k_lo..k_hi, at
+ * most 32 bands (octave -5..4: 31.6 Hz..16 kHz; third-octave -16..13: 25 Hz..
+ * 20 kHz).  A band whose upper edge fm G^(1 / (2 b)) exceeds sr / 2 is
+ * DSP_ERR_INVALID.
+ * Filter.  Zero phase, applied in the frequency domain: bin frequency f is
+ * multiplied by g(f) = 1 / sqrt(1 + (Qd (f / fm - fm / f))^6), g(0) = 0, with
+ * Qr = 1 / (G^(1 / (2 b)) - G^(-1 / (2 b))) and Qd = (pi / 6) / sin(pi / 6) Qr:
+ * the magnitude of the sixth-order Butterworth band filter of IEC 61260 /
+ * ANSI S1.11.  Zero phase means the filter rings symmetrically: a little band
+ * energy lies before the onset (entry 0 below), and ISO 3382's caveat that a
+ * band of width B resolves a decay time T only for B T > 16 applies.  g is
+ * computed per bin in float32 with correctly rounded division and square root.
+ * Transform.  y_{c,b} = irfft_n(g_b rfft_n(in[c]))[0..L) with n the smallest
+ * power of two >= max(1024, L + P), P = ceil(8 sr Qr / fm_lo) for the lowest
+ * band (8 / its bandwidth): the response's slowest pole decays as
+ * e^(-pi B t / 2), so what wraps around into [0, L) is below -100 dB.
+ * n > 2^24 is DSP_ERR_UNSUPPORTED.
+ * Onset, per channel, on the unfiltered row: peak = max |in[c]|, thr = peak *
+ * 0.1f (one float32 product), onset = the first i with |in[c][i]| >= thr (ISO
+ * 3382's -20 dB rule).  Both are exact.  A silent row: peak 0, onset 0, every
+ * energy 0.
+ * Hop.  sr % 100 != 0 is DSP_ERR_UNSUPPORTED; hop = the largest divisor of
+ * sr / 100 that is <= sr / 1000 (48000: 48, 44100: 21, 96000: 96, 88200: 63,
+ * 32000: 32), so 10, 50 and 80 ms are whole hops.  Hop j of channel c covers
+ * [onset_c + j hop, min(L, onset_c + (j + 1) hop)).
+ * Output.  peak[c] and onset[c]; energy[c bands + b], rows of hops =
+ * ceil(L / hop) + 1 float64: entry 0 = sum y^2 over i < onset, entry 1 + j =
+ * sum y^2 over hop j, the rest 0.  moment (may be NULL), the same layout:
+ * sum (i - onset) y^2, in samples.
+ * Summation order (part of the contract): y^2 is one float32 product, taken to
+ * float64.  A hop's samples i = 0 .. are dealt to 16 float64 accumulators, i to
+ * accumulator i mod 16, each added in sample order; the 16 are then added as a
+ * tree, a_q += a_{q ^ 8}, then ^ 4, ^ 2, ^ 1.  Entry 0: the samples before the
+ * onset are cut into pieces of hop samples from sample 0, each summed as a hop;
+ * the pieces p are dealt to 64 accumulators, p to accumulator p mod 64, added in
+ * piece order, and the 64 are added as the same tree from ^ 32 down.  So a row
+ * is a function of hop and the band-filtered samples alone: no float atomics,
+ * the same bits on every run, and (channel, band)'s bits do not depend on C,
+ * the number of bands or the group size.  Accuracy: per row max_j |e - exact|
+ * <= 3.5e-6 max_j exact for finite samples; non-finite samples give undefined
+ * sums and onset.
+ * Method: an integer atomic max over |x| bit patterns and an integer atomic min
+ * over indices (no float atomics) for peak and onset; dsp_rfft's passes for the
+ * channels; per group of (channel, band) rows a mask launch, dsp_irfft's passes
+ * and the hop reduction, which reads the onset on the device: the call does not
+ * synchronise its stream.  The scratch is kept per stream; the rows of a group
+ * are capped at 256 MiB of it (16 rows at most, one at least: 320 MiB at
+ * n = 2^24), see dsp_decay_plan.
+ * DSP_ERR_INVALID for C = 0, L = 0, ex->sample_offset != 0, a bad spec, a
+ * float64 row that is not 8-byte aligned, or any overlap of an output row with
+ * an input row or another output row (nothing is written).  Host rows with
+ * DSP_EXEC_HOST_BUFFERS.  The twiddle table is cached per device: a stream being
+ * captured needs one eager call of the same n first.  DSP_ERR_NO_DEVICE without
+ * a device. */
+typedef struct dsp_decay_spec {
+    uint32_t fraction; /* 1 or 3 */
+    int32_t k_lo, k_hi;
+} dsp_decay_spec;      /* NULL: {1, -5, 4} */
+
+/* The plan (host only, no device).  Any out pointer may be NULL; fm holds 32. */
+int dsp_decay_plan(uint64_t L, uint32_t C, uint32_t sr, const dsp_decay_spec *spec, uint32_t *n, uint32_t *P,
+                   uint32_t *hop, uint32_t *bands, uint64_t *hops, uint64_t *scratch_bytes, double *fm);
+int dsp_decay(const float *const *in, uint32_t C, uint64_t L, uint32_t sr, const dsp_decay_spec *spec, float *peak,
+              uint64_t *onset, double *const *energy, double *const *moment /* may be NULL */, const dsp_exec *ex);
+
+/* From one energy row to the room-acoustic figures (host only, float64).
+ * e_j = energy[1 + j] for the F = (L - onset) / hop full hops (a partial last
+ * hop is ignored); W = (sr / 100) / hop hops are 10 ms.
+ *   noise N      the mean of the last max(1, F / 10) of the e_j
+ *   inr          10 log10(max_k mean(e[k .. k + W)) / N) dB; +inf when N = 0
+ *   truncation   k_t: the first k at or after the loudest window with
+ *                mean(e[k .. k + W)) <= 10^0.3 N, else the start of the noise tail
+ *   EDC_k = sum_{j = k}^{k_t - 1} e_j, L_k = 10 log10(EDC_k / EDC_0) at t_k = k hop / sr
+ *   edt, t20, t30   -60 / slope of the least-squares line of L_k against t_k from
+ *                the first k with L_k <= hi to the last with L_k >= lo, (hi, lo) =
+ *                (0, -10), (-5, -25), (-5, -35), in seconds.  Valid with inr >=
+ *                20 / 35 / 45 dB and at least 3 points; else NaN and the flag bit
+ *   c50, c80     10 log10(early / late) dB, split at 0.05 sr / hop and 0.08 sr /
+ *                hop hops, late summed up to k_t;  d50 = early / (early + late)
+ *   ts           sum moment / sum e over j < k_t, in seconds; NaN without a
+ *                moment row
+ * No noise compensation is done (Lundeby's method is out of scope).  A silent
+ * row (every e_j = 0) sets DSP_DECAY_SILENT, one with F < W DSP_DECAY_SHORT;
+ * both leave every value NaN.  DSP_ERR_INVALID for a NULL energy or res,
+ * onset > L, or a rate and hop other than dsp_decay_plan's. */
+#define DSP_DECAY_SILENT 0x1u
+#define DSP_DECAY_EDT_INVALID 0x2u
+#define DSP_DECAY_T20_INVALID 0x4u
+#define DSP_DECAY_T30_INVALID 0x8u
+#define DSP_DECAY_SHORT 0x10u
+typedef struct dsp_decay_result {
+    double edt, t20, t30;       /* seconds */
+    double c50, c80;            /* dB */
+    double d50;                 /* 0..1 */
+    double ts;                  /* seconds */
+    double inr;                 /* dB */
+    uint32_t flags;             /* DSP_DECAY_* */
+    uint32_t truncation;        /* k_t, in hops from the onset */
+    uint32_t reserved[2];
+} dsp_decay_result;
+int dsp_decay_derive(const double *energy, const double *moment /* may be NULL */, uint64_t L, uint64_t onset,
+                     uint32_t hop, uint32_t sr, dsp_decay_result *res);
+
 /* Test hooks (not for production use).
  * DSP_DEBUG_BIQUAD_SPIN_LIMIT (set): the sleeps a DSP_PLUGIN_BIQUAD look-back
  *   waits for a preceding tile's words before it gives up (value ~0 restores
