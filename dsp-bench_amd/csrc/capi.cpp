@@ -200,9 +200,8 @@ int get_scratch(int dev, hipStream_t s, size_t bytes, float **out, ScratchSlot s
 static std::shared_ptr<SpectrumRow> spectrum_recycle(DeviceRes &r) {
     for (size_t i = 0; i < r.spectrum_retired.size(); ++i) {
         auto &e = r.spectrum_retired[i];
-        bool done = e.use_count() == 1 && hipEventQuery(e->ready) == hipSuccess;
-        for (auto &kv : e->used) done = done && hipEventQuery(kv.second) == hipSuccess;
-        if (!done) continue;
+        if (!spectrum_row_idle(*e, e.use_count(), [](hipEvent_t ev) { return hipEventQuery(ev) == hipSuccess; }))
+            continue;
         std::shared_ptr<SpectrumRow> out = std::move(e);
         r.spectrum_retired.erase(r.spectrum_retired.begin() + (long)i);
         return out;
@@ -218,7 +217,10 @@ int spectrum_row(int dev, hipStream_t s, const std::vector<uint64_t> &key,
         if (e->key == key) {
             // (the stream that computed the row too: a wait on an event of its own costs next to
             // nothing, and a stream handle does not identify a stream once streams are destroyed)
-            DSPB_HIP(hipStreamWaitEvent(s, e->ready, 0));
+            // A completed ready event orders the row before every later launch on any stream:
+            // once it has been seen so, hits enqueue no wait
+            if (spectrum_row_must_wait(*e, [](hipEvent_t ev) { return hipEventQuery(ev) == hipSuccess; }))
+                DSPB_HIP(hipStreamWaitEvent(s, e->ready, 0));
             *out = e;
             return DSP_OK;
         }
@@ -232,6 +234,7 @@ int spectrum_row(int dev, hipStream_t s, const std::vector<uint64_t> &key,
         }
     }
     e->key = key;
+    e->ready_seen = false;
     // with g_mu held, so that a second call of this key finds the event recorded
     int st = compute(e->row);
     if (st == DSP_OK && hipEventRecord(e->ready, s) != hipSuccess) st = DSP_ERR_HIP;
@@ -248,10 +251,17 @@ int spectrum_row(int dev, hipStream_t s, const std::vector<uint64_t> &key,
     return DSP_OK;
 }
 
-int spectrum_row_used(hipStream_t s, const std::shared_ptr<SpectrumRow> &e) {
+int spectrum_row_event(hipStream_t s, const std::shared_ptr<SpectrumRow> &e, hipEvent_t *out) {
     std::lock_guard<std::mutex> lk(g_mu);
     hipEvent_t &ev = e->used[(void *)s];
     if (!ev) DSPB_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    *out = ev;
+    return DSP_OK;
+}
+
+int spectrum_row_used(hipStream_t s, const std::shared_ptr<SpectrumRow> &e) {
+    hipEvent_t ev = nullptr;
+    if (int st = spectrum_row_event(s, e, &ev)) return st;
     DSPB_HIP(hipEventRecord(ev, s));
     return DSP_OK;
 }
@@ -305,8 +315,8 @@ int timing_end(hipStream_t s, TimedLaunch *t, uint64_t bytes) {
 // DSP_DEBUG_FRAME_RUN (stft8192_pk_frame_run) and DSP_DEBUG_BIQUAD_SPIN_LIMIT
 // (capi_render.cpp iir_launch)
 std::atomic<uint32_t> g_frame_run{0}, g_iir_spin_limit{kIirSpinLimit};
-// DSP_DEBUG_SPECTRUM_CACHE and DSP_DEBUG_ROW_RUN (capi_render.cpp dsp_render_stft)
-std::atomic<uint32_t> g_spectrum_cache{0}, g_row_run{0};
+// DSP_DEBUG_SPECTRUM_CACHE, DSP_DEBUG_ROW_RUN and DSP_DEBUG_ROW_PACE (capi_render.cpp dsp_render_stft)
+std::atomic<uint32_t> g_spectrum_cache{0}, g_row_run{0}, g_row_pace{0};
 
 // ---------------------------------------------------------------------------
 // argument checks (before DeviceGuard: they need no device)
@@ -451,6 +461,13 @@ int dsp_debug_set(int what, uint64_t value) {
         g_row_run.store((uint32_t)value);
         return DSP_OK;
     }
+    if (what == DSP_DEBUG_ROW_PACE) {
+        if (value && (value > 0xffffffffull || !row_pace_valid((uint32_t)value)))
+            return invalid("dsp_debug_set: row pace 0x%llx is not nap (0..%u) | waves (%u..9) << 8 [| 1 << 16]",
+                           (unsigned long long)value, kRowPaceMaxNap, kRowPaceMinWaves);
+        g_row_pace.store((uint32_t)value);
+        return DSP_OK;
+    }
     if (what != DSP_DEBUG_BIQUAD_SPIN_LIMIT) return invalid("dsp_debug_set: unknown hook %d", what);
     g_iir_spin_limit.store(value > 0xffffffffull ? kIirSpinLimit : (uint32_t)value);
     return DSP_OK;
@@ -461,8 +478,8 @@ int dsp_debug_get(int what, uint64_t *value) {
         *value = g_frame_run.load();
         return DSP_OK;
     }
-    if ((what == DSP_DEBUG_SPECTRUM_CACHE || what == DSP_DEBUG_ROW_RUN) && value) {
-        *value = (what == DSP_DEBUG_ROW_RUN ? g_row_run : g_spectrum_cache).load();
+    if ((what == DSP_DEBUG_SPECTRUM_CACHE || what == DSP_DEBUG_ROW_RUN || what == DSP_DEBUG_ROW_PACE) && value) {
+        *value = (what == DSP_DEBUG_ROW_RUN ? g_row_run : what == DSP_DEBUG_ROW_PACE ? g_row_pace : g_spectrum_cache).load();
         return DSP_OK;
     }
     if (what != DSP_DEBUG_BIQUAD_REPAIRS || !value) return invalid("dsp_debug_get: unknown hook %d", what);

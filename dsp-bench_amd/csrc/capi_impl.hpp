@@ -3,6 +3,7 @@
 // family) and capi_signal.cpp (the Plugin-free row calls).  Everything here is
 // internal to the library: hidden visibility.
 #pragma once
+#include "spectrum_rules.hpp"
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -73,8 +74,10 @@ struct SpectrumRow {
     std::vector<uint64_t> key;
     float *row = nullptr;              // kSpectrumRowFloats
     hipEvent_t ready = nullptr;        // after the launch that computed the row, on that launch's stream
-    std::map<void *, hipEvent_t> used;  // per stream: after its last launch that read the row
+    bool ready_seen = false;           // `ready` was seen completed: the row is there for every later launch
+    std::map<void *, hipEvent_t> used;  // per stream: completes with its last launch that read the row
 };
+// (the rules of its events: spectrum_rules.hpp)
 constexpr size_t kSpectrumRowFloats = 4100;  // 4097 bins, whole 16-byte pieces
 constexpr size_t kSpectrumRows = 8;          // rows a device keeps
 
@@ -217,11 +220,14 @@ int get_scratch(int dev, hipStream_t s, size_t bytes, float **out, ScratchSlot s
 // The cached spectrum row of `key` on `dev` for launches on s (not while s is
 // being captured).  A miss takes a retired row or allocates one, runs
 // compute(row) -- which enqueues on s the launch that fills it -- and records
-// the entry's ready event; a hit makes s wait for that event.  *out holds the
-// entry until spectrum_row_used(), which the caller calls after its launches
-// that read the row.
+// the entry's ready event; a hit makes s wait for that event unless the event
+// has been seen completed.  *out holds the entry while the caller enqueues.
+// The launch that reads the row on s completes the row's event of that stream,
+// spectrum_row_event(): either as the launch's own completion event
+// (launch_stft8192_rows' `done`) or by spectrum_row_used() after it.
 int spectrum_row(int dev, hipStream_t s, const std::vector<uint64_t> &key,
                  const std::function<int(float *)> &compute, std::shared_ptr<SpectrumRow> *out);
+int spectrum_row_event(hipStream_t s, const std::shared_ptr<SpectrumRow> &e, hipEvent_t *ev);
 int spectrum_row_used(hipStream_t s, const std::shared_ptr<SpectrumRow> &e);
 
 // ---------------------------------------------------------------------------
@@ -245,8 +251,8 @@ constexpr uint32_t kIirSpinLimit = 1u << 16;
 extern std::atomic<uint32_t> g_frame_run, g_iir_spin_limit;
 // DSP_DEBUG_SPECTRUM_CACHE (0: the launch's own choice, 1: wherever it is
 // valid, 2: never) and DSP_DEBUG_ROW_RUN (frames per wave of the store-only
-// launch; 0: kRowRun)
-extern std::atomic<uint32_t> g_spectrum_cache, g_row_run;
+// launch; 0: kRowRun), DSP_DEBUG_ROW_PACE (that launch's pacing; 0: kRowPace)
+extern std::atomic<uint32_t> g_spectrum_cache, g_row_run, g_row_pace;
 
 inline bool is_pow2(uint64_t n) { return n && !(n & (n - 1)); }
 inline uint32_t ilog2(uint64_t n) { uint32_t l = 0; while ((1ull << l) < n) ++l; return l; }

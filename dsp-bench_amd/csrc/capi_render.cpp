@@ -29,6 +29,15 @@ static int launch_stft(const Stft8kArgs &A, uint32_t C, bool fused, hipStream_t 
 // with no FFT to share, the shortest run is the fastest -- 1 is 5% ahead of
 // the reuse launch, 2 level with it, 4 behind it
 constexpr uint32_t kRowRun = 1;
+// ... and its pacing (launch_stft8192_rows): sleep units between a wave's hop
+// burst and its row burst | the waves a CU holds << 8.  Measured in
+// profiles/r10_rows_pacing_ab.txt: 6 waves are 3.5% ahead of the 9 the kernel's
+// LDS tile allows (4 and 5 level with 6, 3 far behind); no sleep beats none in
+// the kernel, though one did in the probe (r10_rows_pacing_probe.txt).
+// kRowPaceRecord on top (DSP_DEBUG_ROW_PACE only) records the row's lifetime
+// event after the launch, as a packet of its own, for the A/B of the launch's
+// own completion event.
+constexpr uint32_t kRowPace = 0u | 6u << 8;
 
 // The device's cached spectrum row for the fused launch A (PER path, H % B ==
 // 0: every frame has the samples of frame 0) on s, not under capture.  The key
@@ -853,7 +862,12 @@ int dsp_render_stft(const float *const *in, uint32_t in_channels, uint64_t L,
             if (A.run > 1 || row) reused = true;
             TimedLaunch tl{};
             if (int e = timing_begin(s, &tl)) return e;
-            if (int e = row ? launch_stft8192_rows(A, cn, row->row, s) : launch_stft(A, cn, true, s)) return e;
+            const uint32_t pace = g_row_pace.load() ? g_row_pace.load() : kRowPace;
+            hipEvent_t row_done = nullptr;  // the row's lifetime event of this stream: completes with the launch
+            if (row && !(pace & kRowPaceRecord))
+                if (int e = spectrum_row_event(s, row, &row_done)) return e;
+            if (int e = row ? launch_stft8192_rows(A, cn, row->row, pace, row_done, s) : launch_stft(A, cn, true, s))
+                return e;
             // algorithmic bytes: render write 4 B + magnitudes 4 K/H B
             // per hop sample, plus the file read when the map uses its input
             const uint64_t hop_samples = (uint64_t)cn * F * H;
@@ -861,7 +875,7 @@ int dsp_render_stft(const float *const *in, uint32_t in_channels, uint64_t L,
             if (map.kind != MapKind::Ramp) bytes += (uint64_t)A.in_ch * F * H * 4;
             if (A.tail_end) bytes += (uint64_t)cn * (A.tail_end - F * (uint64_t)H) * 4;
             if (int e = timing_end(s, &tl, bytes)) return e;
-            return row ? spectrum_row_used(s, row) : (int)DSP_OK;
+            return row && !row_done ? spectrum_row_used(s, row) : (int)DSP_OK;
         });
         if (st) return st;
         if (reused) or_result(ex, DSP_RESULT_FRAME_REUSE);

@@ -330,7 +330,11 @@ int stft_pk_ab_options();  // A/B option bits of this thread: 0 unless the tools
 int launch_stft8192_pk(const Stft8kArgs &A, uint32_t C, bool fused, int opt, hipStream_t s);
 // the PER path with H % B == 0 from a cached spectrum row (4097 magnitudes in
 // bin order): the hops and the rows of every frame, A.run frames per wave, no FFT
-int launch_stft8192_rows(const Stft8kArgs &A, uint32_t C, const float *row, hipStream_t s);
+// pace: nap | waves << 8 (| kRowPaceRecord, which the host side reads); done: may be null
+constexpr uint32_t kRowPaceMaxNap = 16, kRowPaceMinWaves = 3, kRowPaceRecord = 1u << 16;
+bool row_pace_valid(uint32_t pace);
+int launch_stft8192_rows(const Stft8kArgs &A, uint32_t C, const float *row, uint32_t pace, hipEvent_t done,
+                         hipStream_t s);
 int launch_fft_generic(const GenericFftArgs &A, uint64_t transforms, uint32_t C, hipStream_t s);
 int launch_gain(const float *in, float *out, float g, uint64_t n, hipStream_t s);
 int launch_set(float v, float *out, uint64_t n, hipStream_t s);

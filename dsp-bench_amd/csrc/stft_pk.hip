@@ -2,6 +2,7 @@
 // kernels of the headline (PER path, and the store-only launch of a cached
 // spectrum row); the kernels are in stft_pk.hpp.
 #include "stft_pk.hpp"
+#include <hip/hip_ext.h>
 
 namespace dspb {
 
@@ -127,18 +128,32 @@ int launch_stft8192_pk(const Stft8kArgs &A_, uint32_t C, bool fused, int opt, hi
 // stft8192_rows_kernel; in this translation unit, so that a cold headline
 // call still loads one code object): A as for launch_stft8192_pk on the PER
 // path with H % B == 0, A.run frames per wave, `row` the call's 4097 cached
-// magnitudes.
-int launch_stft8192_rows(const Stft8kArgs &A_, uint32_t C, const float *row, hipStream_t stream) {
+// magnitudes.  `pace` (row_pace_valid) is the launch's pacing: an LDS pad
+// beside the kernel's 16,640 B tile leaves pace.waves one-wave workgroups to a
+// CU's 160 KB (the tile alone: 9), and every wave sleeps pace.nap units between
+// its two bursts.  `done`, when set, is an event that completes with the launch
+// (the launch's own completion signal: no packet of its own follows it).
+bool row_pace_valid(uint32_t pace) {
+    const uint32_t nap = pace & 0xffu, waves = (pace >> 8) & 0xffu;
+    return !(pace & ~(0xffffu | kRowPaceRecord)) && nap <= kRowPaceMaxNap && waves >= kRowPaceMinWaves && waves <= 9u;
+}
+int launch_stft8192_rows(const Stft8kArgs &A_, uint32_t C, const float *row, uint32_t pace, hipEvent_t done,
+                         hipStream_t stream) {
     if (A_.F == 0 || C == 0) return DSP_OK;
     Stft8kArgs A = A_;
-    if (!row || !stft8192_pk_per_path(A, true) || A.H % A.map.B != 0 || A.H % 128u != 0 || A.H > 8192u)
+    if (!row || !stft8192_pk_per_path(A, true) || A.H % A.map.B != 0 || A.H % 128u != 0 || A.H > 8192u ||
+        !row_pace_valid(pace))
         return DSP_ERR_INVALID;
+    const uint32_t nap = pace & 0xffu, waves = (pace >> 8) & 0xffu;
+    constexpr uint32_t kLdsPerCu = 160u << 10, kTile = 64u * 65u * 4u;
+    const uint32_t pad = waves >= 9u ? 0u : (kLdsPerCu / waves - kTile) & ~255u;  // (waves >= 3: within 64 KB)
     if (A.run == 0) A.run = 1;
     A.run_waves = (A.F + A.run - 1) / A.run;
     const uint64_t tail = A.tail_end > A.F * A.H ? (A.tail_end - A.F * A.H + A.H - 1) / A.H : 0;
     if (A.run_waves + tail > 0x7fffffffull) return DSP_ERR_INVALID;
     const dim3 grid((uint32_t)(A.run_waves + tail), C);
-#define DSPB_PK_ROWS(p) hipLaunchKernelGGL((stft8192_rows_kernel<p>), grid, dim3(64), 0, stream, A, row)
+#define DSPB_PK_ROWS(p)                                                                                               \
+    hipExtLaunchKernelGGL((stft8192_rows_kernel<p>), grid, dim3(64), pad, stream, nullptr, done, 0, A, row, nap)
     switch (A.map.B <= 128u ? 1u : A.map.B / 128u) {  // the block table's period in 128 samples
     case 1: DSPB_PK_ROWS(1); break;
     case 2: DSPB_PK_ROWS(2); break;

@@ -397,8 +397,14 @@ __device__ __forceinline__ void per_render_tail(const Stft8kArgs &A, uint32_t ch
 // split_y2<KEEP> leaves (M) and stores it nrun times with store_row_pieces --
 // the store instructions, cache policy and addresses of the reuse path.  No
 // window, no FFT, no twiddle loads.
+//
+// Pacing (launch_stft8192_rows, profiles/r10_rows_pacing_probe.txt): the launch
+// is faster with fewer waves pushing stores at once.  The launch's LDS pad sets
+// how many waves a CU holds, and a wave sleeps `nap` x s_sleep(kRowNapUnit)
+// between its hop burst and its row burst.
+constexpr int kRowNapUnit = 16;  // s_sleep(16): 1024 cycles, 0.43 us at 2.4 GHz
 template <int PER>
-__global__ __launch_bounds__(64) void stft8192_rows_kernel(Stft8kArgs A, const float *__restrict__ row) {
+__global__ __launch_bounds__(64) void stft8192_rows_kernel(Stft8kArgs A, const float *__restrict__ row, uint32_t nap) {
     __shared__ __attribute__((aligned(16))) float lds[64 * 65];  // store_row_pieces' tile
     const uint32_t lane = threadIdx.x;
     const uint32_t ch = blockIdx.y;
@@ -416,6 +422,7 @@ __global__ __launch_bounds__(64) void stft8192_rows_kernel(Stft8kArgs A, const f
     per_gather<PER>(A, (uint32_t)(A.goff + fs) + 2u * lane, X);
     float *o = A.out.p[ch] + fs;
     for (uint32_t r = 0; r < nrun; ++r, o += A.H) per_render_hop<PER, !(kPkPerOpt & kPkRenderCached)>(A, o, lane, X);
+    for (uint32_t i = 0; i < nap; ++i) __builtin_amdgcn_s_sleep(kRowNapUnit);
     float M[kPkRowRegs];  // store_row_y2's bins: lane + 64 q, 2048 + that, 4096 - that, 2048 - that
 #pragma unroll
     for (int q = 0; q < 16; ++q) {

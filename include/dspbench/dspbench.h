@@ -674,14 +674,21 @@ int dsp_decay_derive(const double *energy, const double *moment /* may be NULL *
  *   (calls long enough for frame reuse); 1: wherever the row is valid, whatever
  *   the call's length; 2: never (every call takes the reuse launch).
  * DSP_DEBUG_ROW_RUN (set / get): frames per wave of the store-only launch that
- *   serves a cached row (1..65535; 0 restores the default).  Both process-wide:
- *   for tests and A/B runs. */
+ *   serves a cached row (1..65535; 0 restores the default).
+ * DSP_DEBUG_ROW_PACE (set / get): the pacing of that launch, nap | waves << 8:
+ *   a wave sleeps `nap` units (0..16) between its hop stores and its row
+ *   stores, and a compute unit holds `waves` (3..9) of them at once; with
+ *   1 << 16 the row's lifetime event is recorded after the launch and not as
+ *   the launch's own completion.  0 restores the default; the bytes written
+ *   are the same for every value.  All three process-wide: for tests and A/B
+ *   runs. */
 enum {
     DSP_DEBUG_BIQUAD_SPIN_LIMIT = 1,
     DSP_DEBUG_BIQUAD_REPAIRS = 2,
     DSP_DEBUG_FRAME_RUN = 3,
     DSP_DEBUG_SPECTRUM_CACHE = 4,
-    DSP_DEBUG_ROW_RUN = 5
+    DSP_DEBUG_ROW_RUN = 5,
+    DSP_DEBUG_ROW_PACE = 6
 };
 int dsp_debug_set(int what, uint64_t value);
 int dsp_debug_get(int what, uint64_t *value);

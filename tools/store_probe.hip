@@ -6,12 +6,25 @@
 // the two bursts (s_sleep, standing in for the FFT), at the kernel's own
 // occupancy (66.5 KB LDS per 4-wave block -> 2 waves per SIMD).
 //
+//
+// `store_probe rows [passes]` is the store-only launch instead
+// (stft_pk.hpp stft8192_rows_kernel: one-wave workgroups, the XCD remap, the
+// cached row loaded from a 16 KB buffer, store_row_pieces' LDS staging at ld
+// 4097, 32 non-temporal dwordx2 per hop) at its shape, 42,186 frames x 2
+// channels, with the pacing knobs of profiles/r10_rows_pacing_probe.txt:
+// resident waves per CU (an LDS pad), an s_sleep between the hop burst and the
+// row burst, between the two halves of the row burst or as a stagger at wave
+// start, and the order of the two bursts.
+//
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/store_probe.hip -o build/store_probe
 //   ./build/store_probe            (prints one line per variant, GB/s of 8 TB/s)
+//   ./build/store_probe rows 3     (the pacing sweep, three passes)
+//   ./build/store_probe rows 3 fine   (3 to 6 waves, sleeps of 0 to 6 x 64 between the bursts)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <algorithm>
 #include <vector>
 
@@ -103,6 +116,94 @@ __global__ __launch_bounds__(256, 2) void probe(Args A) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// the store-only launch (stft8192_rows_kernel) and its pacing knobs
+// ---------------------------------------------------------------------------
+struct RowsArgs {
+    float *out[2];
+    float *mag[2];
+    const float *row;  // 4100 floats
+    uint64_t F;
+    uint32_t ld;
+    uint32_t mode;  // 0 none, 1 sleep between the bursts, 2 between the halves of the row burst, 3 stagger at wave start
+    uint32_t n;     // s_sleep(64) count
+    uint32_t k;     // mode 3: (wave index mod k) * n sleeps
+};
+
+__device__ __forceinline__ void nap(uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(64);
+}
+
+// store_row_pieces of stft_pk.hpp, with the mode 2 sleep after 8 of its 16 pieces
+__device__ __forceinline__ void rows_pieces(const float (&M)[66], float *mrow, uint32_t lane, float *lds, uint32_t mid) {
+    const uint32_t a = (uint32_t)(reinterpret_cast<uintptr_t>(mrow) >> 2) & 3u;
+    float *sl = lds + a;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        (sl + lane)[64 * q] = M[4 * q];
+        (sl + 2048u + lane)[64 * q] = M[4 * q + 1];
+        (sl + 4096u - lane)[-64 * q] = M[4 * q + 2];
+        (sl + 2048u - lane)[-64 * q] = M[4 * q + 3];
+    }
+    if (lane == 0) {
+        sl[1024] = M[64];
+        sl[3072] = M[65];
+    }
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t j0 = a ? 1u : 0u, j1 = (4093u + a) >> 2;
+    float *gb = mrow - a;  // 16-byte aligned
+    float4 p[16];
+#pragma unroll
+    for (int it = 0; it < 16; ++it) p[it] = reinterpret_cast<const float4 *>(lds)[j0 + 64u * (uint32_t)it + lane];
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int it = 0; it < 16; ++it) {
+        if (it == 8) nap(mid);
+        const uint32_t j = j0 + 64u * (uint32_t)it + lane;
+        if (it < 15 || j <= j1) *reinterpret_cast<v4f *>(gb + 4u * j) = v4f{p[it].x, p[it].y, p[it].z, p[it].w};
+    }
+    const uint32_t head = 4u * j0 - a, tail0 = 4u * j1 + 4u - a;
+    if (lane < head) mrow[lane] = M[0];
+    if (4096u - lane >= tail0) (mrow + 4096u - lane)[0] = M[2];
+}
+
+template <bool ROW_FIRST>
+__global__ __launch_bounds__(64) void rows_probe(RowsArgs A) {
+    __shared__ __attribute__((aligned(16))) float lds[64 * 65];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t ch = blockIdx.y;
+    const uint64_t f = xcd_remap(blockIdx.x, gridDim.x);
+    if (f >= A.F) return;
+    // (blockIdx.x >> 3: the order of the waves one XCD is given)
+    if (A.mode == 3) nap(((blockIdx.x >> 3) % A.k) * A.n);
+    const float v = (float)lane * 0.25f + (float)(f & 511u);
+    const v2f st[4] = {v2f{v, v + 1.f}, v2f{v + 2.f, v + 3.f}, v2f{v + 4.f, v + 5.f}, v2f{v + 6.f, v + 7.f}};
+    float *o = A.out[ch] + f * 4096u;
+    auto hop = [&] {
+#pragma unroll
+        for (int b = 0; b < 32; ++b) __builtin_nontemporal_store(st[b % 4], reinterpret_cast<v2f *>(o + 128u * b) + lane);
+    };
+    auto rowburst = [&] {
+        const float *row = A.row;
+        float M[66];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            M[4 * q] = (row + lane)[64 * q];
+            M[4 * q + 1] = (row + 2048u + lane)[64 * q];
+            M[4 * q + 2] = (row + 4096u - lane)[-64 * q];
+            M[4 * q + 3] = (row + 2048u - lane)[-64 * q];
+        }
+        M[64] = row[1024];
+        M[65] = row[3072];
+        rows_pieces(M, A.mag[ch] + f * A.ld, lane, lds, A.mode == 2 ? A.n : 0u);
+    };
+    if (ROW_FIRST) rowburst(); else hop();
+    if (A.mode == 1) nap(A.n);
+    if (ROW_FIRST) hop(); else rowburst();
+}
+
 __global__ void fill4(float4 *p, uint64_t n4) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n4; i += (uint64_t)gridDim.x * blockDim.x)
         p[i] = float4{1.f, 2.f, 3.f, 4.f};
@@ -128,7 +229,68 @@ static float timeit(K launch, int reps = 20) {
     return ts[ts.size() / 2];
 }
 
-int main() {
+// The sweep: every setting `passes` times, the unpaced launch (9 waves, no
+// sleep, hop first) at the start, the middle and the end of every pass as the
+// session's spread.
+// fine: around the coarse sweep's best corner instead (few waves, hop first, a short sleep between the bursts)
+static int rows_sweep(int passes, bool fine) {
+    const uint64_t F = 42186, L = F * 4096u;
+    const uint32_t ld = 4097;
+    float *out, *row;
+    CK(hipMalloc(&out, (2 * L + 2 * F * ld + 4) * 4));
+    CK(hipMalloc(&row, 4100 * 4));
+    {
+        std::vector<float> h(4100);
+        for (int i = 0; i < 4100; ++i) h[i] = 0.001f * (float)i;
+        CK(hipMemcpy(row, h.data(), 4100 * 4, hipMemcpyHostToDevice));
+    }
+    RowsArgs A;
+    A.out[0] = out; A.out[1] = out + L;
+    A.mag[0] = out + 2 * L; A.mag[1] = A.mag[0] + F * ld;
+    A.row = row; A.F = F; A.ld = ld;
+    const double bytes = 2.0 * F * (4096 + 4097) * 4;
+    const dim3 grid((uint32_t)F, 2);
+    // static LDS 16,640 B of the 160 KB: the pad that leaves `waves` workgroups per CU
+    auto pad_for = [](uint32_t waves) { return waves >= 9 ? 0u : (163840u / waves - 16640u) & ~255u; };
+    auto run = [&](uint32_t waves, bool row_first, uint32_t mode, uint32_t n, uint32_t k) {
+        A.mode = mode; A.n = n; A.k = k ? k : 1;
+        const uint32_t pad = pad_for(waves);
+        const float ms = timeit([&] {
+            if (row_first) rows_probe<true><<<grid, 64, pad>>>(A);
+            else rows_probe<false><<<grid, 64, pad>>>(A);
+        }, 15);
+        CK(hipGetLastError());
+        printf("waves %2u order %s mode %u n %u k %u  %8.4f ms  %7.1f GB/s\n", waves, row_first ? "row-hop" : "hop-row", mode,
+               n, k, ms, bytes / ms / 1e6);
+        fflush(stdout);
+    };
+    for (int pass = 0; pass < passes; ++pass) {
+        printf("-- pass %d\n", pass);
+        run(9, false, 0, 0, 0);
+        if (fine) {
+            for (uint32_t waves : {6u, 5u, 4u, 3u})
+                for (uint32_t n : {0u, 1u, 2u, 3u, 4u, 6u}) run(waves, false, n ? 1 : 0, n, 0);
+            run(9, false, 0, 0, 0);
+            continue;
+        }
+        for (uint32_t waves : {9u, 8u, 6u, 4u}) {
+            if (waves == 6) run(9, false, 0, 0, 0);
+            for (int rf = 0; rf < 2; ++rf) {
+                if (waves != 9 || rf) run(waves, rf, 0, 0, 0);
+                for (uint32_t mode : {1u, 2u})
+                    for (uint32_t n : {1u, 2u, 4u, 8u}) run(waves, rf, mode, n, 0);
+                for (uint32_t k : {2u, 4u})
+                    for (uint32_t n : {1u, 2u, 4u, 8u}) run(waves, rf, 3, n, k);
+            }
+        }
+        run(9, false, 0, 0, 0);
+    }
+    CK(hipDeviceSynchronize());
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "rows")) return rows_sweep(argc > 2 ? atoi(argv[2]) : 3, argc > 3 && !strcmp(argv[3], "fine"));
     const uint64_t F = 84372, L = F * 4096u;
     const uint32_t ldmax = 4224;
     // one allocation: the render rows, then the magnitude rows (the fill
