@@ -214,6 +214,7 @@ enum ScratchSlot : int {
     kScratchBigFft = 5,      // a dsp_rfft / dsp_irfft / dsp_deconvolve / dsp_decay group's work buffers, spectra and rows
     kScratchSpectrumHop = 6, // the hop the one-frame launch of a spectrum-row miss renders beside its row
     kScratchWelch = 7,       // a dsp_welch channel group's chunk of spectra and its runs' partial sums
+    kScratchIstft = 8,       // a dsp_istft channel group's chunk of windowed inverse frames
 };
 int get_scratch(int dev, hipStream_t s, size_t bytes, float **out, ScratchSlot slot);
 

@@ -1,6 +1,7 @@
 // capi_signal.cpp -- the Plugin-free row calls of the C ABI
 // (include/dspbench/dspbench.h): dsp_resample, dsp_loudness, dsp_limiter,
-// dsp_rfft / dsp_irfft, dsp_deconvolve, dsp_sweep, dsp_welch and dsp_decay, with
+// dsp_rfft / dsp_irfft, dsp_deconvolve, dsp_sweep, dsp_welch, dsp_stft / dsp_istft
+// and dsp_decay, with
 // their plans.  Each checks its arguments and its rows' layout before it looks at a
 // device, holds its cached tables until its launches are enqueued, and walks
 // its channels in groups of kMaxChannels.  What it shares with capi.cpp and
@@ -9,6 +10,7 @@
 #include "decay_host.hpp"
 #include "limiter_host.hpp"
 #include "loudness_host.hpp"
+#include "stft_cx_host.hpp"
 #include "sweep_host.hpp"
 #include "welch_host.hpp"
 
@@ -98,6 +100,15 @@ static int welch_plan_checked(uint64_t L, uint32_t C, int has_ref, const dsp_wel
     const char *why = nullptr;
     const int r = welch_plan(L, C, has_ref, spec, p, &why);
     return plan_status(r, why);
+}
+
+static_assert(kStftCxGroup == kMaxChannels, "istft_plan sizes the scratch for for_groups' channel groups");
+// spectrum rows (dsp_stft's outputs, dsp_istft's inputs): none NULL, each 8-byte aligned
+static int spectrum_rows(const char *call, const float *const *rows, uint32_t C) {
+    if (int st = check_rows("spec", rows, C)) return st;
+    for (uint32_t c = 0; c < C; ++c)
+        if (!aligned(rows[c], 8)) return invalid("%s: spec[%u] is not 8-byte aligned", call, c);
+    return DSP_OK;
 }
 
 // float64 output rows (dsp_welch, dsp_decay): none NULL, each 8-byte aligned; *out = the rows as float rows
@@ -774,6 +785,128 @@ int dsp_welch_derive(const double *const *sxx, const double *srr, const double *
     }
     welch_derive(sxx, srr, sxy, C, bins, frames, sr, win_sum, win_sumsq, flags, psd, H1, coherence);
     return DSP_OK;
+}
+
+int dsp_stft_plan(uint64_t L, uint32_t C, const dsp_stft_spec *spec, uint64_t *frames, uint32_t *bins,
+                  uint64_t *min_ld) {
+    StftCxPlan p;
+    const char *why = nullptr;
+    if (int st = plan_status(stft_cx_plan(L, C, spec, &p, &why), why)) return st;
+    if (frames) *frames = p.frames;
+    if (bins) *bins = kStftCxBins;
+    if (min_ld) *min_ld = p.min_ld;
+    return DSP_OK;
+}
+
+int dsp_stft(const float *const *in, uint32_t C, uint64_t L, float *const *spec, uint64_t ld, const dsp_stft_spec *sp,
+             const dsp_exec *ex) {
+    StftCxPlan p;
+    const char *why = nullptr;
+    int st;
+    if ((st = plan_status(stft_cx_plan(L, C, sp, &p, &why), why))) return st;
+    if ((st = plan_status(stft_cx_check_ld(false, p.frames, ld, &why), why))) return st;
+    if ((st = whole_rows_only(ex, "dsp_stft"))) return st;
+    if ((st = check_rows("in", in, C)) || (st = spectrum_rows("dsp_stft", spec, C))) return st;
+    // a row's extent: its last frame ends at 2 K, not at ld
+    const uint64_t span = (p.frames - 1) * ld + 2ull * kStftCxBins;
+    if (rows_overlap(Rows{in, C, L}, Rows{spec, C, span}) || rows_overlap_each_other(Rows{spec, C, span}))
+        return invalid("dsp_stft: an output row overlaps an input row or another output row");
+    DeviceGuard g(ex);
+    if (g.status) return g.status;
+    hipStream_t s = stream_of(ex);
+    Stage stage(ex);
+    const std::vector<const float *> din = stage.in_rows(in, C, L);
+    // host rows: a dense device row each, copied back frame by frame, so that
+    // the floats [2 K, ld) of a frame stay the caller's
+    const uint64_t dense = 2ull * kStftCxBins;
+    std::vector<float *> dspec(C);
+    for (uint32_t c = 0; c < C; ++c) {
+        void *d = spec[c];
+        if (stage.host && (stage.status = stage.alloc(sizeof(float) * p.frames * dense, &d))) break;
+        dspec[c] = (float *)d;
+    }
+    if (stage.status) return stage.status;
+
+    StftCxArgs A{};
+    const float *win = nullptr;
+    if ((st = get_tw(g.dev, s, &A.tw)) || (st = get_window(g.dev, s, p.window, kStftCxN, kStftCxN, &win))) return st;
+    A.win2 = reinterpret_cast<const v2f *>(win);
+    A.H = p.H;
+    A.ld = stage.host ? dense : ld;
+    A.f0 = 0;
+    A.nf = p.frames;
+    st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
+        StftCxArgs G = A;
+        G.cn = cn;
+        group_rows(din, c0, cn, &G.in, 4);
+        group_rows(dspec, c0, cn, &G.spec, 8);
+        return launch_stft_cx(G, s);
+    });
+    if (st) return st;
+    if (stage.host)
+        for (uint32_t c = 0; c < C; ++c)
+            DSPB_HIP(hipMemcpy2DAsync(spec[c], ld * sizeof(float), dspec[c], dense * sizeof(float),
+                                      dense * sizeof(float), p.frames, hipMemcpyDeviceToHost, s));
+    return finish(ex);
+}
+
+int dsp_istft_plan(uint64_t F, uint32_t C, const dsp_istft_spec *spec, uint64_t *Lout, uint32_t *overlap,
+                   uint32_t *chunk, uint64_t *scratch_bytes) {
+    IstftPlan p;
+    const char *why = nullptr;
+    if (int st = plan_status(istft_plan(F, C, spec, &p, &why), why)) return st;
+    if (Lout) *Lout = p.Lout_full;
+    if (overlap) *overlap = p.overlap;
+    if (chunk) *chunk = p.chunk;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    return DSP_OK;
+}
+
+int dsp_istft(const float *const *spec, uint32_t C, uint64_t F, uint64_t ld, float *const *out, uint64_t Lout,
+              const dsp_istft_spec *sp, const dsp_exec *ex) {
+    IstftPlan p;
+    const char *why = nullptr;
+    int st;
+    if ((st = plan_status(istft_plan(F, C, sp, &p, &why), why))) return st;
+    if ((st = plan_status(stft_cx_check_ld(true, F, ld, &why), why))) return st;
+    if ((st = plan_status(istft_check_lout(p, Lout, &why), why))) return st;
+    if ((st = whole_rows_only(ex, "dsp_istft"))) return st;
+    if ((st = spectrum_rows("dsp_istft", spec, C)) || (st = check_rows("out", out, C))) return st;
+    const uint64_t span = (F - 1) * ld + 2ull * kStftCxBins;
+    if (rows_overlap(Rows{spec, C, span}, Rows{out, C, Lout}) || rows_overlap_each_other(Rows{out, C, Lout}))
+        return invalid("dsp_istft: an output row overlaps an input row or another output row");
+    DeviceGuard g(ex);
+    if (g.status) return g.status;
+    hipStream_t s = stream_of(ex);
+    Stage stage(ex);
+    const std::vector<const float *> dspec = stage.in_rows(spec, C, span);
+    const std::vector<float *> dout = stage.out_rows(out, C, Lout);
+    if (stage.status) return stage.status;
+
+    IstftArgs A{};
+    if ((st = get_tw(g.dev, s, &A.tw)) || (st = get_window(g.dev, s, p.window, kStftCxN, kStftCxN, &A.win))) return st;
+    if ((st = get_scratch(g.dev, s, p.scratch_bytes, &A.S, kScratchIstft))) return st;
+    A.win2 = reinterpret_cast<const v2f *>(A.win);
+    A.H = p.H;
+    A.ld = ld;
+    A.F = F;
+    A.slots = p.slots;
+    A.floor = p.floor;
+    st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
+        IstftArgs G = A;
+        G.cn = cn;
+        group_rows(dspec, c0, cn, &G.spec, 8);
+        group_rows(dout, c0, cn, &G.out, 4);
+        for (uint64_t f0 = 0; f0 < F; f0 += p.chunk) {
+            const IstftChunk ch = istft_chunk(p, f0, Lout);
+            if (ch.nf == 0) break;  // past Lout
+            G.fa = ch.fa, G.ns = ch.ns, G.i0 = ch.i0, G.i1 = ch.i1;
+            if (int e = launch_istft_chunk(G, s)) return e;
+        }
+        return (int)DSP_OK;
+    });
+    if (st) return st;
+    return (st = stage.copy_back()) ? st : finish(ex);
 }
 
 int dsp_decay_plan(uint64_t L, uint32_t C, uint32_t sr, const dsp_decay_spec *spec, uint32_t *n, uint32_t *P,

@@ -285,6 +285,41 @@ struct WelchArgs {
     uint32_t first;        // the call's first chunk: the sums start from zero
 };
 int launch_welch_chunk(const WelchArgs &A, hipStream_t s);
+// dsp_stft (stft_cx.hip): the frames [f0, f0 + nf) of one channel group, one
+// wavefront per (frame, row), every bin stored once in natural order
+struct StftCxArgs {
+    ChanIn in;             // cn channel rows
+    ChanOut spec;          // cn spectrum rows, 8-byte aligned: frame f at spec[c] + f ld
+    uint32_t cn;
+    uint64_t f0, nf;
+    uint32_t H;
+    uint64_t ld;           // floats, even, >= 8194
+    const v2f *win2;       // the window as 4096 float2 (w[2m], w[2m+1])
+    const v2f *tw;         // T8192 + lane-major stage twiddles (capi.cpp get_tw)
+};
+int launch_stft_cx(const StftCxArgs &A, hipStream_t s);
+// dsp_istft (stft_cx.hip): one chunk of one channel group (stft_cx_host.hpp
+// istft_chunk): the frames [fa, fa + ns) inverted and windowed into the slots
+// [0, ns) of the scratch, then the samples [i0, i1) summed, divided and stored
+struct IstftArgs {
+    ChanIn spec;           // cn spectrum rows, 8-byte aligned
+    ChanOut out;           // cn output rows
+    uint32_t cn;
+    uint64_t ld;
+    uint32_t H;
+    uint64_t F;            // frames of the call
+    uint64_t fa;           // the frame in slot 0
+    uint32_t ns;           // slots filled, <= slots
+    uint32_t slots;        // slots per row of S
+    uint64_t i0, i1;       // the samples this chunk owns
+    uint32_t t0, n;        // set by the launch: i0 - fa H, and i1 - i0
+    float floor;
+    const v2f *win2;       // the window as 4096 float2, and
+    const float *win;      // the same table as 8192 floats
+    const v2f *tw;
+    float *S;              // [cn][slots][8192] w v_f
+};
+int launch_istft_chunk(const IstftArgs &A, hipStream_t s);
 // dsp_decay (decay.hip): peak and onset of a channel group; the band masks of
 // a group of (channel, band) rows; the rows' hop sums (decay_host.hpp has the
 // scratch layout)

@@ -33,23 +33,6 @@ namespace dspb {
 static_assert(kWelchSpec4 == kConvSpec4, "the forward launch stores conv_fdl.hip's spectrum layout");
 constexpr uint32_t kWelchSlices = kWelchSpec4 / 64;  // 33
 
-// ols_load_frame for a frame that lies wholly inside its row and starts at any
-// sample (an odd hop, a row 4 bytes past a boundary): 4-byte-aligned 8-byte
-// loads, and the window w2[m] = (w[2m], w[2m+1]) applied to the pairs
-typedef v2f v2f_a4 __attribute__((aligned(4)));
-__device__ __forceinline__ void welch_load_frame(const float *x, const v2f *w2, uint32_t lane, cx2 (&P)[32]) {
-    cx v[64];
-#pragma unroll
-    for (int b = 0; b < 64; ++b) {
-        const v2f t = reinterpret_cast<const v2f_a4 *>(x + 128 * b)[lane];
-        const v2f w = w2[64 * b + lane];
-        v[b] = cx{t.x * w.x, t.y * w.y};
-    }
-#pragma unroll
-    for (int j = 0; j < 32; ++j)
-        P[j] = cx2{v2f{v[2 * j].r, v[2 * j + 1].r}, v2f{v[2 * j].i, v[2 * j + 1].i}};
-}
-
 // grid (frame groups of 4, rows); LDS: four 64 x 33 transpose tiles
 __global__ __launch_bounds__(256, 2) void welch_forward_kernel(WelchArgs A) {
     __shared__ __attribute__((aligned(16))) float lds_all[4][64 * 33];

@@ -10,6 +10,7 @@ from .api import (IR_BUFFER_LENGTH, Plugin, conv_plan, deconv_plan, deconvolve, 
                   resample, resample_plan, resample_taps, irfft, rfft, rfft_plan, spectrogram_decimate,
                   stft_frames, stft_magnitude, sweep, sweep_harmonic_offset, sweep_plan,
                   csd, transfer, welch, welch_derive, welch_plan, welch_sums,
+                  istft, istft_plan, stft, stft_plan,
                   decay, decay_derive, decay_energies, decay_plan)
 from . import module, shard, wav  # noqa: F401
 
@@ -18,5 +19,6 @@ __all__ = ["Plugin", "render_offline", "render_loop", "render_stft_host", "minma
            "loudness", "loudness_plan", "loudness_gate", "k_weighting", "limiter", "limiter_plan",
            "rfft", "irfft", "rfft_plan", "deconvolve", "deconv_plan", "sweep", "sweep_plan", "sweep_harmonic_offset",
            "welch", "csd", "transfer", "welch_plan", "welch_sums", "welch_derive",
+           "stft", "istft", "stft_plan", "istft_plan",
            "decay", "decay_plan", "decay_energies", "decay_derive",
            "DSP_WIN_HAMMING", "DSP_WIN_HANN", "DSP_WIN_RECT", "IR_BUFFER_LENGTH", "shard", "wav", "module"]

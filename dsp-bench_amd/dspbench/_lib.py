@@ -104,6 +104,14 @@ class dsp_welch_spec(C.Structure):
 DSP_WELCH_SPECTRUM = 0x1
 
 
+class dsp_stft_spec(C.Structure):
+    _fields_ = [("N", C.c_uint32), ("H", C.c_uint32), ("window", C.c_int32)]
+
+
+class dsp_istft_spec(C.Structure):
+    _fields_ = [("N", C.c_uint32), ("H", C.c_uint32), ("window", C.c_int32), ("floor", C.c_double)]
+
+
 class dsp_decay_spec(C.Structure):
     _fields_ = [("fraction", C.c_uint32), ("k_lo", C.c_int32), ("k_hi", C.c_int32)]
 
@@ -237,6 +245,13 @@ _SIGS = {
                             C.POINTER(dsp_exec)]),
     "dsp_welch_derive": (C.c_int, [DPP, DP, DPP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_double, C.c_double,
                                    C.c_double, C.c_uint32, DPP, DPP, DPP]),
+    "dsp_stft_plan": (C.c_int, [C.c_uint64, C.c_uint32, C.POINTER(dsp_stft_spec), C.POINTER(C.c_uint64),
+                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "dsp_stft": (C.c_int, [FPP, C.c_uint32, C.c_uint64, FPP, C.c_uint64, C.POINTER(dsp_stft_spec), C.POINTER(dsp_exec)]),
+    "dsp_istft_plan": (C.c_int, [C.c_uint64, C.c_uint32, C.POINTER(dsp_istft_spec), C.POINTER(C.c_uint64),
+                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "dsp_istft": (C.c_int, [FPP, C.c_uint32, C.c_uint64, C.c_uint64, FPP, C.c_uint64, C.POINTER(dsp_istft_spec),
+                            C.POINTER(dsp_exec)]),
     "dsp_decay_plan": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(dsp_decay_spec), C.POINTER(C.c_uint32),
                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), DP]),

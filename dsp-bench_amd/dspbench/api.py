@@ -560,6 +560,92 @@ def transfer(ref, x, sr: float, hop: int = 4096, window="hann"):
     return _welch_freqs(sr), d["H1"], d["coherence"]
 
 
+def _stft_window(window):
+    w = _WELCH_WINDOWS.get(window, window) if isinstance(window, str) else window
+    if isinstance(w, str):
+        raise ValueError(f"window {window!r}: 'hann' or 'hamming' (the symmetric tables of stft_magnitude)")
+    return w
+
+
+def stft_plan(L_: int, channels: int = 1, hop: int = 4096, window="hann", N: int = 8192) -> dict:
+    """dsp_stft_plan (host only): frames, bins and the least row stride min_ld (floats)."""
+    sp = L.dsp_stft_spec(N, hop, _stft_window(window))
+    f, b, m = C.c_uint64(), C.c_uint32(), C.c_uint64()
+    check(L.lib().dsp_stft_plan(L_, channels, C.byref(sp), C.byref(f), C.byref(b), C.byref(m)), "dsp_stft_plan")
+    return {"frames": f.value, "bins": b.value, "min_ld": m.value}
+
+
+def istft_plan(frames: int, channels: int = 1, hop: int = 4096, window="hann", floor: float = 1e-10,
+               N: int = 8192) -> dict:
+    """dsp_istft_plan (host only): the full output length N + (F - 1) hop, the
+    frames that touch a sample, the frames per chunk and the device scratch bytes."""
+    sp = L.dsp_istft_spec(N, hop, _stft_window(window), floor)
+    lo, ov, ch, sb = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+    check(L.lib().dsp_istft_plan(frames, channels, C.byref(sp), C.byref(lo), C.byref(ov), C.byref(ch), C.byref(sb)),
+          "dsp_istft_plan")
+    return {"Lout": lo.value, "overlap": ov.value, "chunk": ch.value, "scratch_bytes": sb.value}
+
+
+def _complex_rows(z):
+    """A complex64 [C, F, K] buffer (torch CUDA or numpy, unit stride along K) as
+    (row pointers, the buffer, F, ld in floats)."""
+    if _is_torch(z):
+        import torch
+        assert z.dtype == torch.complex64 and z.dim() == 3 and z.stride(2) == 1
+        assert z.shape[1] == 1 or z.stride(1) >= z.shape[2]
+        return [z[c].data_ptr() for c in range(z.shape[0])], z, int(z.shape[1]), 2 * int(z.stride(1))
+    z = np.asarray(z)
+    assert z.dtype == np.complex64 and z.ndim == 3 and z.strides[2] == 8 and z.strides[1] % 8 == 0
+    return [z[c].ctypes.data for c in range(z.shape[0])], z, int(z.shape[1]), z.strides[1] // 4
+
+
+def stft(x, hop: int = 4096, window="hann", out=None, stream=None):
+    """The complex STFT of the rows of x [C, L] (dsp_stft; torch CUDA tensor, or
+    numpy on the host) over 8192-point frames of hop `hop` under the library's
+    symmetric window, unnormalised: complex64 [C, F, 4097], where x lives.
+    torch.stft(x, 8192, hop, window=w, center=False, return_complex=True), with
+    w that window table, is this result transposed to [C, 4097, F]."""
+    in_ptrs, ref = _rows(x)
+    C_, L_, K = len(in_ptrs), int(x.shape[1]), 4097
+    sp = L.dsp_stft_spec(8192, hop, _stft_window(window))
+    F = stft_plan(L_, C_, hop, window)["frames"]
+    if out is None:
+        if _is_torch(ref):
+            import torch
+            out = torch.empty((C_, F, K), dtype=torch.complex64, device=ref.device)
+        else:
+            out = np.empty((C_, F, K), np.complex64)
+    out_ptrs, _, Fo, ld = _complex_rows(out)
+    assert out.shape[0] == C_ and Fo == F and out.shape[2] == K
+    ex = _exec(ref, 0, stream)
+    check(L.lib().dsp_stft(chan_table(in_ptrs), C_, L_, chan_table(out_ptrs), ld if F > 1 else max(ld, 2 * K),
+                           C.byref(sp), C.byref(ex)), "dsp_stft")
+    return out
+
+
+def istft(Z, hop: int = 4096, window="hann", length: int | None = None, floor: float = 1e-10, out=None, stream=None):
+    """The least-squares overlap-add inverse of a complex spectrogram Z
+    [C, F, 4097] complex64 (dsp_istft; torch CUDA tensor, or numpy on the host)
+    with the analysis window for synthesis: float32 [C, length], length
+    defaulting to 8192 + (F - 1) hop; 512 <= hop <= 8192.  A sample whose sum of
+    squared window values is below `floor` is 0.  istft(stft(x)) is x wherever
+    that sum is not; torch.istft(Z^T, 8192, hop, window=w, center=False) computes
+    the same where its own envelope check lets it (a Hann window's zero ends fail it)."""
+    ptrs, ref, F, ld = _complex_rows(Z)
+    C_ = len(ptrs)
+    assert Z.shape[2] == 4097
+    sp = L.dsp_istft_spec(8192, hop, _stft_window(window), floor)
+    full = istft_plan(F, C_, hop, window, floor)["Lout"]
+    length = full if length is None else length
+    if out is None:
+        out = _alloc_like(ref if _is_torch(ref) else None, (C_, max(length, 1)))
+    out_ptrs, _ = _rows(out)
+    ex = _exec(ref if _is_torch(ref) else None, 0, stream)
+    check(L.lib().dsp_istft(chan_table(ptrs), C_, F, ld if F > 1 else max(ld, 2 * 4097), chan_table(out_ptrs), length,
+                            C.byref(sp), C.byref(ex)), "dsp_istft")
+    return out[:, :length]
+
+
 _DECAY_BANDS = {"octave": (1, -5, 4), "third": (3, -16, 13)}
 _DECAY_FIELDS = ("edt", "t20", "t30", "c50", "c80", "d50", "ts", "inr")
 

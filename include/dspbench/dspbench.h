@@ -544,6 +544,87 @@ int dsp_welch_derive(const double *const *sxx, const double *srr, const double *
                      uint32_t bins, uint64_t frames, double sr, double win_sum, double win_sumsq, uint32_t flags,
                      double *const *psd, double *const *H1, double *const *coherence);
 
+/* The complex STFT and its overlap-add inverse: the pair a spectral process
+ * (a mask, a time-varying EQ, a phase vocoder) stands between.  torch.stft(x,
+ * 8192, H, window=w, center=False, return_complex=True) is dsp_stft's result
+ * transposed to [bins][frames], with w the library's symmetric table.
+ *
+ * N = 8192 only (any other N: DSP_ERR_UNSUPPORTED).  w is DSP_WIN_HAMMING or
+ * DSP_WIN_HANN, the symmetric float table of dsp_stft_magnitude and dsp_welch.
+ * Frames are dsp_stft_frame_count(L, N, H)'s: frame f over [f H, f H + N), no
+ * padding, no centring, a tail shorter than a frame is ignored.  K = 4097 bins.
+ * Normalisation is numpy's (dsp_rfft's): unnormalised forward, 1 / N inverse.
+ *
+ * dsp_stft, 1 <= H <= N:
+ *   spec[c][f ld + 2 k], [.. + 1] = (re, im) of
+ *   X_{c,f}[k] = sum_j w[j] in[c][f H + j] e^(-2 pi i j k / N),  k <= 4096.
+ * ld is in floats, even and >= 2 K = 8194 (the plan's min_ld); floats [2 K, ld)
+ * of a frame are not written.  Rows of spec must be 8-byte aligned; input rows
+ * need only be floats.  The imaginary parts of bins 0 and 4096 are written as
+ * +0.  One launch, no scratch: one wavefront per (frame, row), each bin written
+ * once from registers.  Accuracy: per frame max_k |X - exact| <= 1.1e-6 max_k
+ * |exact| for finite samples.  The same bits on every run; channel c's bits do
+ * not depend on C; scaling the samples by a power of two scales the result
+ * exactly (underflow aside).
+ *
+ * dsp_istft, 512 <= H <= N (a smaller H: DSP_ERR_UNSUPPORTED), the
+ * least-squares (Griffin-Lim) inverse with the same window for synthesis.  With
+ * v_f = irfft_N(spec_f), bins 0 and 4096 taken by their real part only (as
+ * dsp_irfft), and Lout_full = N + (F - 1) H:
+ *   num[i] = sum_f w[i - f H] v_f[i - f H]     den[i] = sum_f w[i - f H]^2
+ *   out[c][i] = den[i] < floor ? 0 : num[i] / den[i],   i < Lout <= Lout_full
+ * over the frames f that cover i, at most overlap = ceil(N / H) <= 16 of them.
+ * floor must be finite and in [1e-12, 1]; a Hann window's zero ends make den 0
+ * at the first and last samples, which is what floor is for.
+ * Summation order (part of the contract): w v_f is one float32 product; num
+ * adds them in float32 in ascending frame order; den adds w^2 in float32 in the
+ * same order, each step one fused multiply-add; the quotient is one correctly
+ * rounded float32 division, den compared with floor rounded to float32.  No
+ * float atomics: the same bits on every run, and channel c's bits do not depend
+ * on C.  A sample whose exact den lies within a factor 2 of floor may come out
+ * either way; everything else follows the rule.  Accuracy: per row
+ * |out[i] - exact[i]| <= 1.1e-6 A[i] max_f max_j |v_f[j]| with the noise gain
+ * A[i] = sum_f |w[i - f H]| / den[i], for finite spectra.
+ * Method: the frames are walked in chunks of `chunk` frames; one launch
+ * inverts a chunk's frames, one wavefront each, and writes w v_f to a device
+ * scratch kept per stream; a second launch, one thread per output sample, sums
+ * and divides.  A chunk's first launch also inverts again the up to overlap - 1
+ * frames before the chunk that its samples still touch, so no sum straddles two
+ * launches.  chunk is the largest count with min(C, 16) chunk 32 KiB <= 64 MiB.
+ *
+ * Both: DSP_ERR_INVALID (nothing written) for C = 0, no frame (L < N, F = 0),
+ * H = 0 or H > N, an unknown window, a floor out of range, ld odd or < 8194,
+ * Lout = 0 or Lout > Lout_full, ex->sample_offset != 0, a spectrum row that is
+ * not 8-byte aligned, or any overlap of an output row with an input row or
+ * another output row.  Host rows with DSP_EXEC_HOST_BUFFERS.  Channel groups of
+ * at most 16 run one after another.  The window and twiddle tables are cached
+ * per device: a stream being captured needs one eager call of the same shape
+ * first.  DSP_ERR_NO_DEVICE without a device. */
+typedef struct dsp_stft_spec {
+    uint32_t N;     /* 8192 */
+    uint32_t H;     /* 1 .. N */
+    int32_t window; /* DSP_WIN_HAMMING or DSP_WIN_HANN */
+} dsp_stft_spec;    /* NULL: {8192, 4096, DSP_WIN_HANN} */
+typedef struct dsp_istft_spec {
+    uint32_t N;     /* 8192 */
+    uint32_t H;     /* 512 .. N */
+    int32_t window; /* DSP_WIN_HAMMING or DSP_WIN_HANN */
+    double floor;   /* 1e-12 .. 1 */
+} dsp_istft_spec;   /* NULL: {8192, 4096, DSP_WIN_HANN, 1e-10} */
+
+/* The plans (host only, no device).  Any out pointer may be NULL.
+ * dsp_stft_plan: frames F, bins K = 4097, min_ld = 2 K floats.
+ * dsp_istft_plan: Lout_full, overlap, chunk, and the bytes of device scratch:
+ * min(C, 16) min(F, chunk + overlap - 1) frames of 32 KiB. */
+int dsp_stft_plan(uint64_t L, uint32_t C, const dsp_stft_spec *spec, uint64_t *frames, uint32_t *bins,
+                  uint64_t *min_ld);
+int dsp_stft(const float *const *in, uint32_t C, uint64_t L, float *const *spec, uint64_t ld,
+             const dsp_stft_spec *sp, const dsp_exec *ex);
+int dsp_istft_plan(uint64_t F, uint32_t C, const dsp_istft_spec *spec, uint64_t *Lout, uint32_t *overlap,
+                   uint32_t *chunk, uint64_t *scratch_bytes);
+int dsp_istft(const float *const *spec, uint32_t C, uint64_t F, uint64_t ld, float *const *out, uint64_t Lout,
+              const dsp_istft_spec *sp, const dsp_exec *ex);
+
 /* Room-acoustic decay analysis (ISO 3382) of C impulse responses of L samples:
  * what an impulse response (dsp_deconvolve) is measured for.  dsp_decay returns
  * per (channel, band) the energy of the band-filtered response in short hops
