@@ -42,6 +42,21 @@
 //                       ir_rate / R (the filter's DC gain is kept); it must still
 //                       be <= 2^20 taps.  Not with --device-rate, --loop or
 //                       --comm-id
+//     --stretch RATE    make the render 1 / RATE times as long at the same pitch
+//                       (dsp_time_stretch: STFT, phase vocoder, inverse STFT at hop
+//                       --stretch-hop, default 2048; 0.125 <= RATE <= 8; the render
+//                       must hold one 8192-point frame), before --normalize, --limit
+//                       and the encode.  Prints one JSON line {"stretch": {rate, p,
+//                       q, hop, frames_in, frames_out, samples_in,
+//                       samples_stretched, samples_out}}
+//     --pitch SEMITONES shift the render's pitch by p / q ~ 2^(SEMITONES / 12)
+//                       (dsp_pitch_ratio, |SEMITONES| <= 24) at its length: the
+//                       render, zero-padded by whole hops as far as needed, is
+//                       stretched at rate q / p to floor(frames p / q + 1 / 2) samples and
+//                       converted from p to q (dsp_resample); samples_out is within
+//                       one of samples_in.  The same JSON line.  Neither goes with
+//                       the other, with --deconvolve, --transfer, --decay, --stft,
+//                       --loop or the multi-GPU modes
 //     --loudness        measure the render (its written frames, every output
 //                       channel at weight 1: dsp_loudness with the true peak)
 //                       and print one JSON line with the result to stdout
@@ -694,6 +709,50 @@ int render(Render &r, time_t started) {
     return 0;
 }
 
+// --stretch RATE / --pitch SEMITONES: the render made 1 / RATE times as long at its pitch
+// (dsp_time_stretch), or shifted by p / q ~ 2^(SEMITONES / 12) at its length: stretched at rate
+// q / p and converted from p to q (dsp_resample) by dsp_pitch_shift_plan's lengths: the render
+// zero-padded by whole hops until the stretch reaches floor(Lr p / q + 1 / 2) samples.  One JSON line tells the figures.
+int stretch(Render &r) {
+    const Options &o = r.o;
+    hipStream_t s = r.dev.stream.h;
+    uint32_t p = 1, q = 1;
+    int st;
+    dsp_stretch_spec sp{o.stretch_rate, N, o.stretch_hop, DSP_WIN_HANN, 1e-10};
+    const uint64_t L0 = r.Lr;
+    uint64_t Lin = L0, fin = 0, fout = 0, Lout = 0;
+    if (o.pitch && (st = dsp_pitch_shift_plan(L0, r.C, o.pitch_semitones, o.stretch_hop, DSP_WIN_HANN, &p, &q, &sp, &Lin,
+                                              &Lout, nullptr)))
+        return fail("dsp_pitch_shift_plan", st);
+    if ((st = dsp_time_stretch_plan(Lin, r.C, &sp, &fin, &fout, nullptr, o.pitch ? nullptr : &Lout, nullptr)))
+        return fail("dsp_time_stretch_plan", st);
+    const double rate = sp.rate;
+    if (Lin > L0) {  // the render, then silence
+        Rows padded;
+        HIPCK(padded.alloc(r.C, Lin));
+        for (uint32_t c = 0; c < r.C; ++c) {
+            HIPCK(hipMemcpyAsync(padded.ptr[c], r.out.ptr[c], L0 * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIPCK(hipMemsetAsync(padded.ptr[c] + L0, 0, (Lin - L0) * sizeof(float), s));
+        }
+        HIPCK(hipStreamSynchronize(s));
+        for (uint32_t c = 0; c < r.C; ++c) r.out.replace(c, std::move(padded.own[c]));
+    }
+    Rows now;
+    HIPCK(now.alloc(r.C, Lout));
+    if ((st = dsp_time_stretch(r.out.ptr.data(), r.C, Lin, now.ptr.data(), Lout, &sp, &r.dev.ex)))
+        return fail("dsp_time_stretch", st);
+    HIPCK(hipStreamSynchronize(s));
+    for (uint32_t c = 0; c < r.C; ++c) r.out.replace(c, std::move(now.own[c]));
+    r.Lr = Lout;
+    if (o.pitch)
+        if (int e = resample_rows(r.out, r.C, r.Lr, p, q, " (--pitch)", [](uint64_t) { return 0; }, r.dev)) return e;
+    std::printf("{\"stretch\": {\"rate\": %s, \"p\": %u, \"q\": %u, \"hop\": %u, \"frames_in\": %llu, "
+                "\"frames_out\": %llu, \"samples_in\": %llu, \"samples_stretched\": %llu, \"samples_out\": %llu}}\n",
+                json_num(rate).c_str(), p, q, o.stretch_hop, (unsigned long long)fin, (unsigned long long)fout,
+                (unsigned long long)L0, (unsigned long long)Lout, (unsigned long long)r.Lr);
+    return 0;
+}
+
 std::string loudness_json(const Options &o, const dsp_loudness_result &lr, float g, const dsp_limiter_result &lim,
                           float residual) {
     std::string j = "{\"integrated\": " + json_num(lr.integrated) + ", \"range\": " + json_num(lr.range) +
@@ -830,6 +889,8 @@ int run_render(const Options &o, time_t started) {
     if (int e = make_plugin(r)) return e;
     if (int e = render(r, started)) return e;
     if (o.multi() && o.rank != 0) return finish_rank(r);
+    if (o.stretches())  // before the levels and the encode: they see what is written
+        if (int e = stretch(r)) return e;
     if (o.loudness || o.normalize)
         if (int e = level(r)) return e;
     if (int e = write_outputs(r)) return e;

@@ -60,6 +60,9 @@ const struct {
     {"--true-peak-ceiling", true, given<number<&O::ceiling_dbtp>, &O::ceiling>},
     {"--limit-lookahead", true, number<&O::limit_lookahead_ms>},
     {"--limit-release", true, number<&O::limit_release_ms>},
+    {"--stretch", true, given<number<&O::stretch_rate>, &O::stretch>},
+    {"--pitch", true, given<number<&O::pitch_semitones>, &O::pitch>},
+    {"--stretch-hop", true, given<u32<&O::stretch_hop>, &O::have_stretch_hop>},
     {"--loop", true, u64<&O::loop_blocks>},
     {"--world", true, u32<&O::world>},
     {"--rank", true, given<u32<&O::rank>, &O::have_rank>},
@@ -77,6 +80,23 @@ const struct {
     {[](const O &o) { return o.block == 0; }, nullptr, true},
     {[](const O &o) { return o.have_plugin && !o.conv_path.empty(); },
      "dspbench_render: --convolve and --plugin exclude each other\n", false},
+    {[](const O &o) { return o.stretches() && (!o.deconv_path.empty() || !o.transfer_path.empty()); },
+     "dspbench_render: --stretch and --pitch exclude --deconvolve and --transfer (they change a render, and those "
+     "modes measure a recording)\n", true},
+    {[](const O &o) {
+         return o.stretches() && (!o.decay_path.empty() || o.decay_alone || !o.stft_path.empty() || o.loop_blocks || o.multi_gpu());
+     },
+     "dspbench_render: --stretch and --pitch exclude --decay, --stft, --loop and the multi-GPU modes\n", true},
+    {[](const O &o) { return o.stretch && o.pitch; },
+     "dspbench_render: --stretch and --pitch exclude each other\n", true},
+    {[](const O &o) { return o.stretch && !(o.stretch_rate >= 0.125 && o.stretch_rate <= 8.0); },
+     "dspbench_render: --stretch RATE must lie in 0.125 .. 8\n", true},
+    {[](const O &o) { return o.pitch && !(o.pitch_semitones >= -24.0 && o.pitch_semitones <= 24.0); },
+     "dspbench_render: --pitch SEMITONES must lie in -24 .. 24\n", true},
+    {[](const O &o) { return o.have_stretch_hop && !o.stretches(); },
+     "dspbench_render: --stretch-hop needs --stretch or --pitch\n", true},
+    {[](const O &o) { return o.have_stretch_hop && (o.stretch_hop < 512 || o.stretch_hop > 8192); },
+     "dspbench_render: --stretch-hop H must lie in 512 .. 8192\n", true},
     {[](const O &o) {
          return !o.deconv_path.empty() && (o.have_plugin || !o.conv_path.empty() || o.loop_blocks || o.multi_gpu() ||
                                            o.rate || !o.stft_path.empty() || o.levels());
@@ -161,6 +181,7 @@ const char *usage_text() {
            "       [--loudness] [--normalize LUFS [--true-peak-ceiling DBTP [--limit]]]\n"
            "       [--limit-lookahead MS] [--limit-release MS]\n"
            "       [--deconvolve REF.wav [--deconv-eps E] [--deconv-pre N] [--ir-length N]]\n"
+           "       [--stretch RATE | --pitch SEMITONES [--stretch-hop H]]\n"
            "       [--psd OUT.csv] [--decay OUT.csv [--decay-bands octave|third]]\n"
            "       [--world W --rank R --comm-id FILE [--run-id STR] [--chunk SAMPLES]]\n"
            "       dspbench_render REC.wav OUT.csv --transfer REF.wav [--device N]\n"

@@ -16,6 +16,10 @@ struct Options {
     bool have_decay_bands = false, decay_alone = false;
     bool have_plugin = false, have_rank = false;
     bool loudness = false, normalize = false, ceiling = false, limit = false;
+    // --stretch RATE | --pitch SEMITONES [--stretch-hop H]: of the render, before the levels and the encode
+    bool stretch = false, pitch = false, have_stretch_hop = false;
+    double stretch_rate = 1.0, pitch_semitones = 0.0;
+    uint32_t stretch_hop = 2048;
     float gain = -1.f, ir_gain = 0.9f, ir_step = 0.002f;
     double deconv_eps = 1e-6, norm_lufs = 0.0, ceiling_dbtp = 0.0, limit_lookahead_ms = 1.5, limit_release_ms = 100.0;
     uint64_t deconv_pre = 0, ir_length = 0, loop_blocks = 0, chunk = 16ull << 20;
@@ -27,6 +31,7 @@ struct Options {
     std::string sweep_bits = "float";
 
     // the groups the exclusion rules speak of
+    bool stretches() const { return stretch || pitch; }
     bool levels() const { return loudness || normalize || ceiling || limit; }
     bool multi() const { return !comm_path.empty(); }
     bool multi_gpu() const { return multi() || world; }

@@ -317,6 +317,8 @@ int timing_end(hipStream_t s, TimedLaunch *t, uint64_t bytes) {
 std::atomic<uint32_t> g_frame_run{0}, g_iir_spin_limit{kIirSpinLimit};
 // DSP_DEBUG_SPECTRUM_CACHE, DSP_DEBUG_ROW_RUN and DSP_DEBUG_ROW_PACE (capi_render.cpp dsp_render_stft)
 std::atomic<uint32_t> g_spectrum_cache{0}, g_row_run{0}, g_row_pace{0};
+// DSP_DEBUG_PVOC_CHUNK and DSP_DEBUG_PVOC_VARIANT (capi_signal.cpp dsp_pvoc)
+std::atomic<uint32_t> g_pvoc_chunk{0}, g_pvoc_variant{0};
 
 // ---------------------------------------------------------------------------
 // argument checks (before DeviceGuard: they need no device)
@@ -468,6 +470,16 @@ int dsp_debug_set(int what, uint64_t value) {
         g_row_pace.store((uint32_t)value);
         return DSP_OK;
     }
+    if (what == DSP_DEBUG_PVOC_CHUNK) {
+        if (value && (value < 8 || value > 4096)) return invalid("dsp_debug_set: pvoc chunk %llu is not 0 or 8..4096", (unsigned long long)value);
+        g_pvoc_chunk.store((uint32_t)value);
+        return DSP_OK;
+    }
+    if (what == DSP_DEBUG_PVOC_VARIANT) {
+        if (value > 7) return invalid("dsp_debug_set: pvoc variant %llu > 7", (unsigned long long)value);
+        g_pvoc_variant.store((uint32_t)value);
+        return DSP_OK;
+    }
     if (what != DSP_DEBUG_BIQUAD_SPIN_LIMIT) return invalid("dsp_debug_set: unknown hook %d", what);
     g_iir_spin_limit.store(value > 0xffffffffull ? kIirSpinLimit : (uint32_t)value);
     return DSP_OK;
@@ -480,6 +492,10 @@ int dsp_debug_get(int what, uint64_t *value) {
     }
     if ((what == DSP_DEBUG_SPECTRUM_CACHE || what == DSP_DEBUG_ROW_RUN || what == DSP_DEBUG_ROW_PACE) && value) {
         *value = (what == DSP_DEBUG_ROW_RUN ? g_row_run : what == DSP_DEBUG_ROW_PACE ? g_row_pace : g_spectrum_cache).load();
+        return DSP_OK;
+    }
+    if ((what == DSP_DEBUG_PVOC_CHUNK || what == DSP_DEBUG_PVOC_VARIANT) && value) {
+        *value = (what == DSP_DEBUG_PVOC_CHUNK ? g_pvoc_chunk : g_pvoc_variant).load();
         return DSP_OK;
     }
     if (what != DSP_DEBUG_BIQUAD_REPAIRS || !value) return invalid("dsp_debug_get: unknown hook %d", what);

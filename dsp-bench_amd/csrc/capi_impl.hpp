@@ -215,6 +215,7 @@ enum ScratchSlot : int {
     kScratchSpectrumHop = 6, // the hop the one-frame launch of a spectrum-row miss renders beside its row
     kScratchWelch = 7,       // a dsp_welch channel group's chunk of spectra and its runs' partial sums
     kScratchIstft = 8,       // a dsp_istft channel group's chunk of windowed inverse frames
+    kScratchPvoc = 9,        // a dsp_pvoc channel group's chunk phase sums and carries
 };
 int get_scratch(int dev, hipStream_t s, size_t bytes, float **out, ScratchSlot slot);
 
@@ -254,6 +255,9 @@ extern std::atomic<uint32_t> g_frame_run, g_iir_spin_limit;
 // valid, 2: never) and DSP_DEBUG_ROW_RUN (frames per wave of the store-only
 // launch; 0: kRowRun), DSP_DEBUG_ROW_PACE (that launch's pacing; 0: kRowPace)
 extern std::atomic<uint32_t> g_spectrum_cache, g_row_run, g_row_pace;
+// DSP_DEBUG_PVOC_CHUNK (output frames per chunk of dsp_pvoc; 0: kPvocChunk) and
+// DSP_DEBUG_PVOC_VARIANT (the A/B bits of pvoc.hip; 0: the product)
+extern std::atomic<uint32_t> g_pvoc_chunk, g_pvoc_variant;
 
 inline bool is_pow2(uint64_t n) { return n && !(n & (n - 1)); }
 inline uint32_t ilog2(uint64_t n) { uint32_t l = 0; while ((1ull << l) < n) ++l; return l; }

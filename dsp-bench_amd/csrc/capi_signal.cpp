@@ -1,7 +1,7 @@
 // capi_signal.cpp -- the Plugin-free row calls of the C ABI
 // (include/dspbench/dspbench.h): dsp_resample, dsp_loudness, dsp_limiter,
-// dsp_rfft / dsp_irfft, dsp_deconvolve, dsp_sweep, dsp_welch, dsp_stft / dsp_istft
-// and dsp_decay, with
+// dsp_rfft / dsp_irfft, dsp_deconvolve, dsp_sweep, dsp_welch, dsp_stft / dsp_istft,
+// dsp_pvoc / dsp_time_stretch and dsp_decay, with
 // their plans.  Each checks its arguments and its rows' layout before it looks at a
 // device, holds its cached tables until its launches are enqueued, and walks
 // its channels in groups of kMaxChannels.  What it shares with capi.cpp and
@@ -10,6 +10,7 @@
 #include "decay_host.hpp"
 #include "limiter_host.hpp"
 #include "loudness_host.hpp"
+#include "pvoc_host.hpp"
 #include "stft_cx_host.hpp"
 #include "sweep_host.hpp"
 #include "welch_host.hpp"
@@ -103,7 +104,8 @@ static int welch_plan_checked(uint64_t L, uint32_t C, int has_ref, const dsp_wel
 }
 
 static_assert(kStftCxGroup == kMaxChannels, "istft_plan sizes the scratch for for_groups' channel groups");
-// spectrum rows (dsp_stft's outputs, dsp_istft's inputs): none NULL, each 8-byte aligned
+static_assert(kPvocGroup == kMaxChannels, "pvoc_plan sizes the scratch for for_groups' channel groups");
+// spectrum rows (dsp_stft's outputs, dsp_istft's inputs, both of dsp_pvoc's): none NULL, each 8-byte aligned
 static int spectrum_rows(const char *call, const float *const *rows, uint32_t C) {
     if (int st = check_rows("spec", rows, C)) return st;
     for (uint32_t c = 0; c < C; ++c)
@@ -907,6 +909,172 @@ int dsp_istft(const float *const *spec, uint32_t C, uint64_t F, uint64_t ld, flo
     });
     if (st) return st;
     return (st = stage.copy_back()) ? st : finish(ex);
+}
+
+int dsp_pvoc_plan(uint64_t F, uint32_t C, const dsp_pvoc_spec *spec, uint64_t *frames_out, uint32_t *chunk,
+                  uint64_t *scratch_bytes) {
+    PvocPlan p;
+    const char *why = nullptr;
+    if (int st = plan_status(pvoc_plan(F, C, spec, &p, &why, g_pvoc_chunk.load()), why)) return st;
+    if (frames_out) *frames_out = p.frames_out;
+    if (chunk) *chunk = p.chunk;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    return DSP_OK;
+}
+
+int dsp_pvoc(const float *const *spec_in, uint32_t C, uint64_t F, uint64_t ld_in, float *const *spec_out,
+             uint64_t ld_out, const dsp_pvoc_spec *sp, const dsp_exec *ex) {
+    PvocPlan p;
+    const char *why = nullptr;
+    int st;
+    if ((st = plan_status(pvoc_plan(F, C, sp, &p, &why, g_pvoc_chunk.load()), why))) return st;
+    if ((st = plan_status(pvoc_check_ld(F, ld_in, &why), why))) return st;
+    if ((st = plan_status(pvoc_check_ld(p.frames_out, ld_out, &why), why))) return st;
+    if ((st = whole_rows_only(ex, "dsp_pvoc"))) return st;
+    if ((st = spectrum_rows("dsp_pvoc", spec_in, C)) || (st = spectrum_rows("dsp_pvoc", spec_out, C))) return st;
+    // a row's extent: its last frame ends at 2 K, not at ld
+    const uint64_t dense = 2ull * kStftCxBins;
+    const uint64_t span_in = (F - 1) * ld_in + dense, span_out = (p.frames_out - 1) * ld_out + dense;
+    if (rows_overlap(Rows{spec_in, C, span_in}, Rows{spec_out, C, span_out}) ||
+        rows_overlap_each_other(Rows{spec_out, C, span_out}))
+        return invalid("dsp_pvoc: an output row overlaps an input row or another output row");
+    DeviceGuard g(ex);
+    if (g.status) return g.status;
+    hipStream_t s = stream_of(ex);
+    Stage stage(ex);
+    const std::vector<const float *> din = stage.in_rows(spec_in, C, span_in);
+    // host rows: a dense device row each, copied back frame by frame (as dsp_stft does)
+    std::vector<float *> dout(C);
+    for (uint32_t c = 0; c < C; ++c) {
+        void *d = spec_out[c];
+        if (stage.host && (stage.status = stage.alloc(sizeof(float) * p.frames_out * dense, &d))) break;
+        dout[c] = (float *)d;
+    }
+    if (stage.status) return stage.status;
+
+    PvocArgs A{};
+    float *scratch = nullptr;
+    // (the A/B variant that stores every increment keeps them behind the sums)
+    A.variant = g_pvoc_variant.load();
+    const uint64_t inc_bytes = (A.variant & 4u) ? (uint64_t)p.rows * p.frames_out * kStftCxBins * sizeof(uint32_t) : 0;
+    if ((st = get_scratch(g.dev, s, p.scratch_bytes + inc_bytes, &scratch, kScratchPvoc))) return st;
+    A.S = reinterpret_cast<uint32_t *>(scratch);
+    A.inc = inc_bytes ? A.S + p.scratch_bytes / sizeof(uint32_t) : nullptr;
+    A.ld_in = ld_in;
+    A.ld_out = stage.host ? dense : ld_out;
+    A.F = F;
+    A.frames_out = p.frames_out;
+    A.rate = p.rate;
+    A.chunk = p.chunk;
+    A.chunks = p.chunks;
+    st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
+        PvocArgs G = A;
+        G.cn = cn;
+        group_rows(din, c0, cn, &G.in, 8);
+        group_rows(dout, c0, cn, &G.out, 8);
+        return launch_pvoc(G, s);
+    });
+    if (st) return st;
+    if (stage.host)
+        for (uint32_t c = 0; c < C; ++c)
+            DSPB_HIP(hipMemcpy2DAsync(spec_out[c], ld_out * sizeof(float), dout[c], dense * sizeof(float),
+                                      dense * sizeof(float), p.frames_out, hipMemcpyDeviceToHost, s));
+    return finish(ex);
+}
+
+int dsp_time_stretch_plan(uint64_t L, uint32_t C, const dsp_stretch_spec *spec, uint64_t *frames_in,
+                          uint64_t *frames_out, uint64_t *Lout_full, uint64_t *Lout_default,
+                          uint64_t *device_bytes) {
+    StretchPlan p;
+    const char *why = nullptr;
+    if (int st = plan_status(stretch_plan(L, C, spec, &p, &why), why)) return st;
+    if (frames_in) *frames_in = p.frames_in;
+    if (frames_out) *frames_out = p.frames_out;
+    if (Lout_full) *Lout_full = p.Lout_full;
+    if (Lout_default) *Lout_default = p.Lout_default;
+    if (device_bytes) *device_bytes = p.device_bytes;
+    return DSP_OK;
+}
+
+namespace {
+// the two spectrograms of a dsp_time_stretch call: freed when the call returns
+struct StretchScratch {
+    float *a = nullptr, *b = nullptr;
+    ~StretchScratch() {
+        (void)hipFree(a);
+        (void)hipFree(b);
+    }
+};
+}  // namespace
+
+int dsp_time_stretch(const float *const *in, uint32_t C, uint64_t L, float *const *out, uint64_t Lout,
+                     const dsp_stretch_spec *sp, const dsp_exec *ex) {
+    StretchPlan p;
+    const char *why = nullptr;
+    int st;
+    if ((st = plan_status(stretch_plan(L, C, sp, &p, &why), why))) return st;
+    if (Lout == 0 || Lout > p.Lout_full) return invalid("dsp_time_stretch: needs 1 <= Lout <= N + (F' - 1) H");
+    if ((st = whole_rows_only(ex, "dsp_time_stretch"))) return st;
+    if ((st = check_rows("in", in, C)) || (st = check_rows("out", out, C))) return st;
+    if (rows_overlap(Rows{in, C, L}, Rows{out, C, Lout}) || rows_overlap_each_other(Rows{out, C, Lout}))
+        return invalid("dsp_time_stretch: an output row overlaps an input row or another output row");
+    DeviceGuard g(ex);
+    if (g.status) return g.status;
+    hipStream_t s = stream_of(ex);
+    if ((st = refuse_capture(s, "dsp_time_stretch's pair of spectrograms (allocated per call)"))) return st;
+    Stage stage(ex);
+    const std::vector<const float *> din = stage.in_rows(in, C, L);
+    const std::vector<float *> dout = stage.out_rows(out, C, Lout);
+    if (stage.status) return stage.status;
+    StretchScratch sc;
+    hipError_t me = hipMalloc(&sc.a, p.in_bytes);
+    if (me == hipSuccess) me = hipMalloc(&sc.b, p.out_bytes);
+    if (me != hipSuccess) {
+        (void)hipGetLastError();  // the refusal is this call's answer, not a later launch's
+        return hip_fail(me, "dsp_time_stretch: hipMalloc of the spectrograms");
+    }
+    // the three public calls on device rows, on the caller's stream
+    dsp_exec dev{};
+    dev.device = g.dev;
+    dev.stream = (void *)s;
+    st = for_groups(C, [&](uint32_t c0, uint32_t cn) {
+        const float *zin[kMaxChannels];
+        float *zout[kMaxChannels];
+        for (uint32_t j = 0; j < cn; ++j) {
+            zin[j] = sc.a + (uint64_t)j * p.frames_in * p.ld;
+            zout[j] = sc.b + (uint64_t)j * p.frames_out * p.ld;
+        }
+        if (int e = dsp_stft(din.data() + c0, cn, L, const_cast<float *const *>(zin), p.ld, &p.fwd, &dev)) return e;
+        if (int e = dsp_pvoc(zin, cn, p.frames_in, p.ld, zout, p.ld, &p.pv, &dev)) return e;
+        return dsp_istft(zout, cn, p.frames_out, p.ld, dout.data() + c0, Lout, &p.inv, &dev);
+    });
+    if (!st) st = stage.copy_back();
+    // the spectrograms leave with the call: what was enqueued must have read them
+    const hipError_t e = hipStreamSynchronize(s);
+    if (st) return st;
+    DSPB_HIP(e);
+    return finish(ex);
+}
+
+int dsp_pitch_shift_plan(uint64_t L, uint32_t C, double semitones, uint32_t H, int32_t window, uint32_t *p, uint32_t *q,
+                         dsp_stretch_spec *stretch, uint64_t *padded, uint64_t *stretched, uint64_t *Lout) {
+    PitchPlan pl;
+    const char *why = nullptr;
+    if (int st = plan_status(pitch_plan(L, C, semitones, H, window, &pl, &why), why)) return st;
+    ResamplePlan rp;
+    if (int st = resample_plan_checked(pl.p, pl.q, pl.stretched, nullptr, &rp)) return st;
+    if (p) *p = pl.p;
+    if (q) *q = pl.q;
+    if (stretch) *stretch = pl.stretch;
+    if (padded) *padded = pl.padded;
+    if (stretched) *stretched = pl.stretched;
+    if (Lout) *Lout = rp.Lout;
+    return DSP_OK;
+}
+
+int dsp_pitch_ratio(double semitones, uint32_t *p, uint32_t *q) {
+    const char *why = nullptr;
+    return plan_status(pitch_ratio(semitones, p, q, &why), why);
 }
 
 int dsp_decay_plan(uint64_t L, uint32_t C, uint32_t sr, const dsp_decay_spec *spec, uint32_t *n, uint32_t *P,

@@ -320,6 +320,23 @@ struct IstftArgs {
     float *S;              // [cn][slots][8192] w v_f
 };
 int launch_istft_chunk(const IstftArgs &A, hipStream_t s);
+// dsp_pvoc (pvoc.hip): one channel group, all of its chunks (pvoc_host.hpp
+// PvocPlan): the chunks' phase sums, their carries, then the output frames
+struct PvocArgs {
+    ChanIn in;             // cn spectrum rows of F frames, 8-byte aligned
+    ChanOut out;           // cn spectrum rows of frames_out frames, 8-byte aligned
+    uint32_t cn;
+    uint64_t ld_in, ld_out;  // floats, even, >= 8194
+    uint64_t F, frames_out;
+    double rate;
+    uint32_t chunk;        // output frames per chunk
+    uint64_t chunks;       // ceil(frames_out / chunk)
+    uint64_t c0;           // set by the launch: its first chunk
+    uint32_t *S;           // [cn][chunks][4097]
+    uint32_t variant;      // 0: the product; else the A/B bits of DSP_DEBUG_PVOC_VARIANT (pvoc.hip)
+    uint32_t *inc;         // variant bit 4 only: [cn][frames_out][4097] increments
+};
+int launch_pvoc(const PvocArgs &A, hipStream_t s);
 // dsp_decay (decay.hip): peak and onset of a channel group; the band masks of
 // a group of (channel, band) rows; the rows' hop sums (decay_host.hpp has the
 // scratch layout)

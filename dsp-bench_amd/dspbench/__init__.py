@@ -11,6 +11,7 @@ from .api import (IR_BUFFER_LENGTH, Plugin, conv_plan, deconv_plan, deconvolve, 
                   stft_frames, stft_magnitude, sweep, sweep_harmonic_offset, sweep_plan,
                   csd, transfer, welch, welch_derive, welch_plan, welch_sums,
                   istft, istft_plan, stft, stft_plan,
+                  phase_vocoder, pitch_ratio, pitch_shift, pitch_shift_plan, pvoc_plan, time_stretch, time_stretch_plan,
                   decay, decay_derive, decay_energies, decay_plan)
 from . import module, shard, wav  # noqa: F401
 
@@ -20,5 +21,6 @@ __all__ = ["Plugin", "render_offline", "render_loop", "render_stft_host", "minma
            "rfft", "irfft", "rfft_plan", "deconvolve", "deconv_plan", "sweep", "sweep_plan", "sweep_harmonic_offset",
            "welch", "csd", "transfer", "welch_plan", "welch_sums", "welch_derive",
            "stft", "istft", "stft_plan", "istft_plan",
+           "phase_vocoder", "pvoc_plan", "time_stretch", "time_stretch_plan", "pitch_ratio", "pitch_shift", "pitch_shift_plan",
            "decay", "decay_plan", "decay_energies", "decay_derive",
            "DSP_WIN_HAMMING", "DSP_WIN_HANN", "DSP_WIN_RECT", "IR_BUFFER_LENGTH", "shard", "wav", "module"]

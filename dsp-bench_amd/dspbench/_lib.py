@@ -112,6 +112,15 @@ class dsp_istft_spec(C.Structure):
     _fields_ = [("N", C.c_uint32), ("H", C.c_uint32), ("window", C.c_int32), ("floor", C.c_double)]
 
 
+class dsp_pvoc_spec(C.Structure):
+    _fields_ = [("rate", C.c_double)]
+
+
+class dsp_stretch_spec(C.Structure):
+    _fields_ = [("rate", C.c_double), ("N", C.c_uint32), ("H", C.c_uint32), ("window", C.c_int32),
+                ("floor", C.c_double)]
+
+
 class dsp_decay_spec(C.Structure):
     _fields_ = [("fraction", C.c_uint32), ("k_lo", C.c_int32), ("k_hi", C.c_int32)]
 
@@ -252,6 +261,19 @@ _SIGS = {
                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "dsp_istft": (C.c_int, [FPP, C.c_uint32, C.c_uint64, C.c_uint64, FPP, C.c_uint64, C.POINTER(dsp_istft_spec),
                             C.POINTER(dsp_exec)]),
+    "dsp_pvoc_plan": (C.c_int, [C.c_uint64, C.c_uint32, C.POINTER(dsp_pvoc_spec), C.POINTER(C.c_uint64),
+                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "dsp_pvoc": (C.c_int, [FPP, C.c_uint32, C.c_uint64, C.c_uint64, FPP, C.c_uint64, C.POINTER(dsp_pvoc_spec),
+                           C.POINTER(dsp_exec)]),
+    "dsp_time_stretch_plan": (C.c_int, [C.c_uint64, C.c_uint32, C.POINTER(dsp_stretch_spec), C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_uint64)]),
+    "dsp_time_stretch": (C.c_int, [FPP, C.c_uint32, C.c_uint64, FPP, C.c_uint64, C.POINTER(dsp_stretch_spec),
+                                   C.POINTER(dsp_exec)]),
+    "dsp_pitch_ratio": (C.c_int, [C.c_double, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "dsp_pitch_shift_plan": (C.c_int, [C.c_uint64, C.c_uint32, C.c_double, C.c_uint32, C.c_int32, C.POINTER(C.c_uint32),
+                                       C.POINTER(C.c_uint32), C.POINTER(dsp_stretch_spec), C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "dsp_decay_plan": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(dsp_decay_spec), C.POINTER(C.c_uint32),
                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), DP]),

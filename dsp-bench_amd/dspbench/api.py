@@ -646,6 +646,112 @@ def istft(Z, hop: int = 4096, window="hann", length: int | None = None, floor: f
     return out[:, :length]
 
 
+def pvoc_plan(frames: int, rate: float, channels: int = 1) -> dict:
+    """dsp_pvoc_plan (host only): the output frames of `frames` input frames at
+    `rate`, the output frames per chunk and the device scratch bytes."""
+    sp = L.dsp_pvoc_spec(rate)
+    fo, ch, sb = C.c_uint64(), C.c_uint32(), C.c_uint64()
+    check(L.lib().dsp_pvoc_plan(frames, channels, C.byref(sp), C.byref(fo), C.byref(ch), C.byref(sb)), "dsp_pvoc_plan")
+    return {"frames": fo.value, "chunk": ch.value, "scratch_bytes": sb.value}
+
+
+def phase_vocoder(Z, rate: float, out=None, stream=None):
+    """The phase vocoder on a complex spectrogram Z [C, F, 4097] complex64
+    (dsp_pvoc; torch CUDA tensor, or numpy on the host): complex64
+    [C, F', 4097] where Z lives, F' = pvoc_plan(F, rate)["frames"]; rate > 1
+    shortens.  librosa.phase_vocoder(Z^T, rate=rate)'s recurrence, the phase
+    carried as a 32-bit fixed-point fraction of a turn."""
+    ptrs, ref, F, ld = _complex_rows(Z)
+    C_, K = len(ptrs), 4097
+    assert Z.shape[2] == K
+    sp = L.dsp_pvoc_spec(rate)
+    Fo = pvoc_plan(F, rate, C_)["frames"]
+    if out is None:
+        if _is_torch(ref):
+            import torch
+            out = torch.empty((C_, Fo, K), dtype=torch.complex64, device=ref.device)
+        else:
+            out = np.empty((C_, Fo, K), np.complex64)
+    out_ptrs, _, Fout, ld_out = _complex_rows(out)
+    assert out.shape[0] == C_ and Fout == Fo and out.shape[2] == K
+    ex = _exec(ref if _is_torch(ref) else None, 0, stream)
+    check(L.lib().dsp_pvoc(chan_table(ptrs), C_, F, ld if F > 1 else max(ld, 2 * K), chan_table(out_ptrs),
+                           ld_out if Fo > 1 else max(ld_out, 2 * K), C.byref(sp), C.byref(ex)), "dsp_pvoc")
+    return out
+
+
+def _stretch_spec(rate, hop, window, floor):
+    return L.dsp_stretch_spec(rate, 8192, hop, _stft_window(window), floor)
+
+
+def time_stretch_plan(L_: int, rate: float, channels: int = 1, hop: int = 2048, window="hann",
+                      floor: float = 1e-10) -> dict:
+    """dsp_time_stretch_plan (host only): frames in and out, the full and the
+    default output length, and the bytes of the two device spectrograms."""
+    sp = _stretch_spec(rate, hop, window, floor)
+    fi, fo, lf, ld, db = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(L.lib().dsp_time_stretch_plan(L_, channels, C.byref(sp), C.byref(fi), C.byref(fo), C.byref(lf), C.byref(ld),
+                                        C.byref(db)), "dsp_time_stretch_plan")
+    return {"frames_in": fi.value, "frames_out": fo.value, "Lout_full": lf.value, "Lout": ld.value,
+            "device_bytes": db.value}
+
+
+def time_stretch(x, rate: float, hop: int = 2048, window="hann", length: int | None = None, floor: float = 1e-10,
+                 out=None, stream=None):
+    """x [C, L] (torch CUDA tensor, or numpy on the host) made 1 / rate times as
+    long at the same pitch (dsp_time_stretch: stft, phase_vocoder, istft at hop
+    `hop`): float32 [C, length], length defaulting to round(L / rate) (at most
+    the plan's Lout_full)."""
+    in_ptrs, ref = _rows(x)
+    C_, L_ = len(in_ptrs), int(x.shape[1])
+    p = time_stretch_plan(L_, rate, C_, hop, window, floor)
+    length = p["Lout"] if length is None else length
+    if out is None:
+        out = _alloc_like(ref, (C_, max(length, 1)))
+    out_ptrs, _ = _rows(out)
+    sp = _stretch_spec(rate, hop, window, floor)
+    ex = _exec(ref, 0, stream)
+    check(L.lib().dsp_time_stretch(chan_table(in_ptrs), C_, L_, chan_table(out_ptrs), length, C.byref(sp),
+                                   C.byref(ex)), "dsp_time_stretch")
+    return out[:, :length]
+
+
+def pitch_ratio(semitones: float) -> tuple[int, int]:
+    """dsp_pitch_ratio (host only): (p, q), p / q the best approximation of
+    2^(semitones / 12) with p, q <= 4096."""
+    p, q = C.c_uint32(), C.c_uint32()
+    check(L.lib().dsp_pitch_ratio(semitones, C.byref(p), C.byref(q)), "dsp_pitch_ratio")
+    return p.value, q.value
+
+
+def pitch_shift_plan(L_: int, semitones: float, channels: int = 1, hop: int = 2048, window="hann") -> dict:
+    """dsp_pitch_shift_plan (host only): (p, q) = pitch_ratio(semitones), rate = q / p,
+    `stretched` = floor(L_ p / q + 1 / 2), `padded` = the least max(L_, 8192) + j hop whose
+    time_stretch_plan reaches `stretched` samples -- a stretch to a longer row ends
+    (8192 - hop) (1 / rate - 1) samples early without it -- and Lout = resample_plan's
+    length of `stretched` samples from p to q, within a sample of L_."""
+    p, q, sp = C.c_uint32(), C.c_uint32(), L.dsp_stretch_spec()
+    pad, st, lo = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(L.lib().dsp_pitch_shift_plan(L_, channels, semitones, hop, _stft_window(window), C.byref(p), C.byref(q),
+                                       C.byref(sp), C.byref(pad), C.byref(st), C.byref(lo)), "dsp_pitch_shift_plan")
+    return {"p": p.value, "q": q.value, "rate": sp.rate, "padded": pad.value, "stretched": st.value, "Lout": lo.value}
+
+
+def pitch_shift(x, semitones: float, hop: int = 2048, window="hann"):
+    """x [C, L] shifted by `semitones` at (within a sample) the same length, by the two public
+    calls: with pl = pitch_shift_plan(L, semitones), x zero-padded to pl["padded"] samples,
+    time_stretch(., pl["rate"], length=pl["stretched"]) and resample(., p, q)."""
+    L_ = int(x.shape[1])
+    pl = pitch_shift_plan(L_, semitones, int(x.shape[0]), hop, window)
+    if pl["padded"] > L_:
+        if _is_torch(x):
+            import torch
+            x = torch.nn.functional.pad(x, (0, pl["padded"] - L_))
+        else:
+            x = np.pad(np.asarray(x), ((0, 0), (0, pl["padded"] - L_)))
+    return resample(time_stretch(x, pl["rate"], hop, window, length=pl["stretched"]), pl["p"], pl["q"])
+
+
 _DECAY_BANDS = {"octave": (1, -5, 4), "third": (3, -16, 13)}
 _DECAY_FIELDS = ("edt", "t20", "t30", "c50", "c80", "d50", "ts", "inr")
 

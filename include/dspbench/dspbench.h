@@ -545,7 +545,8 @@ int dsp_welch_derive(const double *const *sxx, const double *srr, const double *
                      double *const *psd, double *const *H1, double *const *coherence);
 
 /* The complex STFT and its overlap-add inverse: the pair a spectral process
- * (a mask, a time-varying EQ, a phase vocoder) stands between.  torch.stft(x,
+ * (a mask, a time-varying EQ, the phase vocoder dsp_pvoc below) stands between.
+ * torch.stft(x,
  * 8192, H, window=w, center=False, return_complex=True) is dsp_stft's result
  * transposed to [bins][frames], with w the library's symmetric table.
  *
@@ -624,6 +625,111 @@ int dsp_istft_plan(uint64_t F, uint32_t C, const dsp_istft_spec *spec, uint64_t 
                    uint32_t *chunk, uint64_t *scratch_bytes);
 int dsp_istft(const float *const *spec, uint32_t C, uint64_t F, uint64_t ld, float *const *out, uint64_t Lout,
               const dsp_istft_spec *sp, const dsp_exec *ex);
+
+/* The phase vocoder: the spectral process that changes a spectrogram's frame
+ * count, and with dsp_stft before and dsp_istft after it a file's duration
+ * (dsp_time_stretch) or, with dsp_resample after that, its pitch.
+ *
+ * dsp_pvoc.  spec_in[c] holds F frames and spec_out[c] F' frames in dsp_stft's
+ * layout: K = 4097 (re, im) pairs per frame, ld_in and ld_out in floats, even
+ * and >= 8194, rows 8-byte aligned; floats [2 K, ld_out) of an output frame are
+ * not written.  rate is finite and in [1/8, 8]; above 1 the output is shorter.
+ * Output frame t reads at s_t = fl64(t rate), one float64 product, and F' is
+ * the number of t >= 0 with s_t < F (ceil(F / rate) up to that rounding; the
+ * plan counts it exactly).  With f = floor(s_t), a = float32(s_t - f) and
+ * Z[F] = Z[F + 1] = 0, per bin k <= 4096, all bins alike as complex values:
+ *   mag_t       = (1 - a) |Z[f]| + a |Z[f + 1]|
+ *   phase_0     = arg Z[0]
+ *   phase_{t+1} = phase_t + arg(Z[f + 1] conj Z[f])        (mod one turn)
+ *   Z'[t]       = mag_t (cos phase_t, sin phase_t)
+ * with arg 0 = 0 (an increment is 0 where either bin is 0).  This is
+ * librosa.phase_vocoder's recurrence: its expected advance cancels modulo a
+ * turn, so no hop enters.
+ * Arithmetic (part of the contract).  A phase is a 32-bit fixed-point fraction
+ * of a turn.  The argument of an input bin is computed in float32 as turns in
+ * [-1/2, 1/2] and rounded to nearest into that format, +1/2 and -1/2 being the
+ * same word; an increment is the wrapping 32-bit difference of the two
+ * arguments, and the phase their wrapping sum.  Integer addition is
+ * associative, so the sum over t is cut into chunks of `chunk` output frames
+ * and gives the same bits however it is cut: the same bits on every run,
+ * channel c's bits do not depend on C, frame t's bits do not depend on how
+ * many frames follow it, no float atomics, and no workgroup waits for
+ * another.  |Z|, the interpolation, cos and sin are float32; scaling Z by a
+ * power of two scales Z' exactly (overflow of |Z|^2 and underflow aside); an
+ * all-zero spectrogram gives +0.  Accuracy against the same recurrence in
+ * float64 on the same float32 input: per bin |Z'[t] - exact| <= 6.2e-7 sqrt(t + 1)
+ * mag_t plus a float32 ulp of the frame's largest magnitude.
+ * Method: three launches per channel group.  Per (chunk, 64 neighbouring bins)
+ * the integer sum of the chunk's increments goes to a device scratch kept per
+ * stream, [row][chunk][4097] uint32; one thread per (row, bin) turns the sums
+ * into each chunk's starting phase; the third launch forms the increments
+ * again, carries the phase and writes every output bin once.  chunk = 64.
+ * DSP_ERR_INVALID (nothing written) for C = 0, F = 0, a NULL spec, a rate that
+ * is not finite or outside [1/8, 8], an odd or short ld, a NULL or misaligned
+ * row, ex->sample_offset != 0, or any overlap of an output row with an input
+ * row or another output row; DSP_ERR_UNSUPPORTED for F > 2^48.  Host rows with
+ * DSP_EXEC_HOST_BUFFERS.  Channel groups of at most 16 run one after another.
+ * The scratch is made on first use: a stream being captured needs one eager
+ * call of the same shape first.  DSP_ERR_NO_DEVICE without a device.
+ *
+ * dsp_time_stretch: dsp_stft(N, H, window), dsp_pvoc(rate), dsp_istft(N, H,
+ * window, floor) over two dense device spectrograms of min(C, 16) rows
+ * (frames_in and frames_out frames of 8194 floats; device_bytes is their sum:
+ * about 5.5 GB per stereo hour and spectrogram at H = 2048).  They are
+ * allocated for the call and freed after it, so this call synchronises its
+ * stream and cannot be captured into a graph (DSP_ERR_INVALID on a capturing
+ * stream); DSP_ERR_NOMEM when they cannot be had.  N = 8192; 512 <= H <= 8192
+ * and the floor rule are dsp_istft's.  Lout_full = N + (F' - 1) H and
+ * Lout_default = min(Lout_full, round(L / rate)); any 1 <= Lout <= Lout_full is
+ * accepted.  What the three calls refuse, this one refuses with the same
+ * status.  Output rows must not overlap input rows or each other.
+ *
+ * dsp_pitch_ratio (host only): the best p / q to 2^(semitones / 12) with p, q
+ * <= 4096, by continued fractions (the nearest of the last convergent and the
+ * last semiconvergent; the nearer to the reciprocal for an upward shift);
+ * |semitones| <= 24, else DSP_ERR_INVALID.  A pitch shift by p / q is
+ * dsp_time_stretch(rate = q / p) followed by dsp_resample(sr_in = p, sr_out =
+ * q).  For the length to come back the stretch must deliver stretched =
+ * floor(L p / q + 1 / 2) samples, and dsp_time_stretch of the L samples alone
+ * ends short of that for an upward shift: its Lout_full is N + (F' - 1) H, about
+ * (N - H)(1 / rate - 1) samples less, because the last input frame starts N - H
+ * before the end.  So the input is first zero-padded: dsp_pitch_shift_plan
+ * (host only) gives p, q, the stretch's spec (rate = q / p, N, H, window, floor
+ * 1e-10), `padded` = the least max(L, 8192) + j H whose Lout_full reaches
+ * `stretched`, `stretched` itself, and Lout = dsp_resample_plan(p, q,
+ * stretched)'s length, within a sample of L (`stretched` is at least 1, so a
+ * row shorter than q / (2 p) comes back up to q / p samples long).  The shift is
+ * then: pad the rows
+ * with zeros to `padded` samples, dsp_time_stretch(., padded, ., stretched,
+ * stretch), dsp_resample(., stretched, ., Lout, p, q).  What
+ * dsp_time_stretch_plan or dsp_resample_plan refuses, the plan refuses with the
+ * same status; L = 0 is DSP_ERR_INVALID.  Any out pointer may be NULL. */
+typedef struct dsp_pvoc_spec {
+    double rate; /* 1/8 .. 8 */
+} dsp_pvoc_spec;
+typedef struct dsp_stretch_spec {
+    double rate;    /* 1/8 .. 8 */
+    uint32_t N;     /* 8192 */
+    uint32_t H;     /* 512 .. N; 2048 is the usual choice */
+    int32_t window; /* DSP_WIN_HAMMING or DSP_WIN_HANN */
+    double floor;   /* 1e-12 .. 1; 1e-10 is the usual choice */
+} dsp_stretch_spec;
+
+/* The plans (host only, no device).  Any out pointer may be NULL.
+ * dsp_pvoc_plan: F', chunk, and the bytes of device scratch: min(C, 16)
+ * ceil(F' / chunk) rows of 4097 uint32. */
+int dsp_pvoc_plan(uint64_t F, uint32_t C, const dsp_pvoc_spec *spec, uint64_t *frames_out, uint32_t *chunk,
+                  uint64_t *scratch_bytes);
+int dsp_pvoc(const float *const *spec_in, uint32_t C, uint64_t F, uint64_t ld_in, float *const *spec_out,
+             uint64_t ld_out, const dsp_pvoc_spec *spec, const dsp_exec *ex);
+int dsp_time_stretch_plan(uint64_t L, uint32_t C, const dsp_stretch_spec *spec, uint64_t *frames_in,
+                          uint64_t *frames_out, uint64_t *Lout_full, uint64_t *Lout_default,
+                          uint64_t *device_bytes);
+int dsp_time_stretch(const float *const *in, uint32_t C, uint64_t L, float *const *out, uint64_t Lout,
+                     const dsp_stretch_spec *spec, const dsp_exec *ex);
+int dsp_pitch_ratio(double semitones, uint32_t *p, uint32_t *q);
+int dsp_pitch_shift_plan(uint64_t L, uint32_t C, double semitones, uint32_t H, int32_t window, uint32_t *p, uint32_t *q,
+                         dsp_stretch_spec *stretch, uint64_t *padded, uint64_t *stretched, uint64_t *Lout);
 
 /* Room-acoustic decay analysis (ISO 3382) of C impulse responses of L samples:
  * what an impulse response (dsp_deconvolve) is measured for.  dsp_decay returns
@@ -762,14 +868,26 @@ int dsp_decay_derive(const double *energy, const double *moment /* may be NULL *
  *   1 << 16 the row's lifetime event is recorded after the launch and not as
  *   the launch's own completion.  0 restores the default; the bytes written
  *   are the same for every value.  All three process-wide: for tests and A/B
- *   runs. */
+ *   runs.
+ * DSP_DEBUG_PVOC_CHUNK (set / get): output frames per chunk of dsp_pvoc and of
+ *   dsp_pvoc_plan (8..4096; 0 restores 64).  The output's bits do not depend on it.
+ * DSP_DEBUG_PVOC_VARIANT (set / get): the A/B variants of dsp_pvoc's kernels, a
+ *   sum of 1 (an increment is one argument of the product Z[f + 1] conj Z[f]
+ *   instead of the difference of two argument words), 2 (cos and sin by the
+ *   hardware's turn-based instructions) and 4 (the first launch stores every
+ *   increment in min(C, 16) F' 4097 more uint32 of scratch and the third reads
+ *   them back).  0 restores the product; 1 and 2 change the output within the
+ *   documented accuracy, 4 does not change it.  Both process-wide: for
+ *   tools/ab_pvoc.py. */
 enum {
     DSP_DEBUG_BIQUAD_SPIN_LIMIT = 1,
     DSP_DEBUG_BIQUAD_REPAIRS = 2,
     DSP_DEBUG_FRAME_RUN = 3,
     DSP_DEBUG_SPECTRUM_CACHE = 4,
     DSP_DEBUG_ROW_RUN = 5,
-    DSP_DEBUG_ROW_PACE = 6
+    DSP_DEBUG_ROW_PACE = 6,
+    DSP_DEBUG_PVOC_CHUNK = 7,
+    DSP_DEBUG_PVOC_VARIANT = 8
 };
 int dsp_debug_set(int what, uint64_t value);
 int dsp_debug_get(int what, uint64_t *value);
