@@ -1,12 +1,12 @@
 // capi.cpp -- the extern "C" boundary of libdspbench (include/dspbench/dspbench.h):
-// what its three translation units share (capi_impl.hpp) and the small services.
+// what its five translation units share (capi_impl.hpp) and the small services.
 //
 // Owns the errors, the per-device constant tables (twiddles, windows: the
 // analogue of the IPP FFT spec / plan cache of dsp.cpp:84-95 and
 // IPP_FFT_Context, structs.h:170-178), the table caches, the per-stream
 // scratch, the kernel timing and the debug hooks; the Plugin family is in
-// capi_render.cpp, the Plugin-free row calls in capi_signal.cpp.  Fails loudly
-// (negative status) on anything it cannot run on the GPU -- there is no CPU
+// capi_render.cpp, the Plugin-free row calls in capi_rate.cpp, capi_bigfft.cpp
+// and capi_grid.cpp.  Fails loudly (negative status) on anything it cannot run on the GPU -- there is no CPU
 // path here.
 #include <cstdarg>
 
@@ -317,7 +317,7 @@ int timing_end(hipStream_t s, TimedLaunch *t, uint64_t bytes) {
 std::atomic<uint32_t> g_frame_run{0}, g_iir_spin_limit{kIirSpinLimit};
 // DSP_DEBUG_SPECTRUM_CACHE, DSP_DEBUG_ROW_RUN and DSP_DEBUG_ROW_PACE (capi_render.cpp dsp_render_stft)
 std::atomic<uint32_t> g_spectrum_cache{0}, g_row_run{0}, g_row_pace{0};
-// DSP_DEBUG_PVOC_CHUNK and DSP_DEBUG_PVOC_VARIANT (capi_signal.cpp dsp_pvoc)
+// DSP_DEBUG_PVOC_CHUNK and DSP_DEBUG_PVOC_VARIANT (capi_grid.cpp dsp_pvoc)
 std::atomic<uint32_t> g_pvoc_chunk{0}, g_pvoc_variant{0};
 
 // ---------------------------------------------------------------------------
@@ -327,6 +327,18 @@ int check_rows(const char *name, const float *const *rows, uint32_t n) {
     if (n && !rows) return invalid("%s is NULL", name);
     for (uint32_t c = 0; c < n; ++c)
         if (!rows[c]) return invalid("%s[%u] is NULL", name, c);
+    return DSP_OK;
+}
+
+int double_rows(const char *call, const char *name, double *const *rows, uint32_t C,
+                std::vector<const float *> *out) {
+    if (!rows) return invalid("%s is NULL", name);
+    out->resize(C);
+    for (uint32_t c = 0; c < C; ++c) {
+        if (!rows[c]) return invalid("%s[%u] is NULL", name, c);
+        if (!aligned(rows[c], 8)) return invalid("%s: %s[%u] is not 8-byte aligned", call, name, c);
+        (*out)[c] = reinterpret_cast<const float *>(rows[c]);
+    }
     return DSP_OK;
 }
 

@@ -1,7 +1,8 @@
 // capi_impl.hpp -- what the C ABI's translation units share: capi.cpp (errors,
 // per-device resources, the small services), capi_render.cpp (the Plugin
-// family) and capi_signal.cpp (the Plugin-free row calls).  Everything here is
-// internal to the library: hidden visibility.
+// family) and the Plugin-free row calls: capi_rate.cpp (rate and level),
+// capi_bigfft.cpp (the large FFT) and capi_grid.cpp (the 8192-point grid).
+// Everything here is internal to the library: hidden visibility.
 #pragma once
 #include "spectrum_rules.hpp"
 #include <hip/hip_runtime.h>
@@ -271,10 +272,22 @@ inline uint64_t goff_of(const dsp_exec *ex) { return ex ? ex->sample_offset : 0;
 // argument checks (before DeviceGuard: they need no device)
 // ---------------------------------------------------------------------------
 int check_rows(const char *name, const float *const *rows, uint32_t n);
+// float64 output rows (dsp_welch, dsp_decay): none NULL, each 8-byte aligned; *out = the rows as float rows
+int double_rows(const char *call, const char *name, double *const *rows, uint32_t C, std::vector<const float *> *out);
 // "<call>: whole rows only (sample_offset 0)"
 int whole_rows_only(const dsp_exec *ex, const char *call);
 // a host plan's (0 | 1 | 2, why) as DSP_OK | DSP_ERR_INVALID | DSP_ERR_UNSUPPORTED and the error text
 int plan_status(int r, const char *why);
+// ... of plan(args..., &why)
+template <class Plan, class... A>
+int plan_checked(Plan plan, A &&...a) {
+    const char *why = nullptr;
+    const int r = plan(std::forward<A>(a)..., &why);
+    return plan_status(r, why);
+}
+// dsp_resample_plan's checks and the library's ResamplePlan (NULL spec: the defaults; capi_rate.cpp)
+int resample_plan_checked(uint32_t sr_in, uint32_t sr_out, uint64_t L, const dsp_resample_spec *spec,
+                          ResamplePlan *plan);
 
 // ---------------------------------------------------------------------------
 // host-buffer staging (DSP_EXEC_HOST_BUFFERS), one Stage per call.  Device
@@ -283,12 +296,17 @@ int plan_status(int r, const char *why);
 // stream, the outputs copied back by copy_back(); finish() then synchronises.
 // The first failure sticks in `status` (checked once after the call's in() /
 // out()s); zero-length buffers are one float and are not copied.
+// Framed rows (dsp_stft, dsp_pvoc: `frames` frames of `dense` floats, `ld`
+// floats apart): the device row of a host row is dense -- the launch's leading
+// dimension is framed_ld() -- and copy_back() copies it out frame by frame, so
+// that the floats [dense, ld) of a frame stay the caller's.
 // ---------------------------------------------------------------------------
 struct Stage {
     const bool host;
     const hipStream_t s;
     int status = DSP_OK;
-    struct Back { void *host; const void *dev; size_t bytes; };
+    // pitch 0: `bytes` in one piece; else `frames` pieces of `bytes`, `pitch` bytes apart at the host
+    struct Back { void *host; const void *dev; size_t bytes, pitch, frames; };
     std::vector<void *> bufs;
     std::vector<Back> back;
 
@@ -316,7 +334,18 @@ struct Stage {
     void *out_bytes(void *p, size_t bytes) {
         if (!host) return p;
         void *d;
-        if ((status = alloc(bytes, &d)) == DSP_OK) back.push_back(Back{p, d, bytes});
+        if ((status = alloc(bytes, &d)) == DSP_OK) back.push_back(Back{p, d, bytes, 0, 1});
+        return d;
+    }
+    uint64_t framed_ld(uint64_t dense, uint64_t ld) const { return host ? dense : ld; }
+    std::vector<float *> out_framed_rows(float *const *rows, uint32_t C, uint64_t frames, uint64_t dense, uint64_t ld) {
+        std::vector<float *> d(C);
+        for (uint32_t c = 0; c < C; ++c) {
+            void *p = rows[c];
+            if (host && (status = alloc(sizeof(float) * frames * dense, &p)) == DSP_OK)
+                back.push_back(Back{rows[c], p, dense * sizeof(float), ld * sizeof(float), frames});
+            d[c] = (float *)p;
+        }
         return d;
     }
     const float *in(const float *p, uint64_t n) { return (const float *)in_bytes(p, n * sizeof(float)); }
@@ -332,14 +361,30 @@ struct Stage {
         return d;
     }
     int copy_back() {  // in the order of the out()s
-        for (const Back &b : back)
-            if (int st = copy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost)) return st;
+        for (const Back &b : back) {
+            if (b.pitch)
+                DSPB_HIP(hipMemcpy2DAsync(b.host, b.pitch, b.dev, b.bytes, b.bytes, b.frames, hipMemcpyDeviceToHost, s));
+            else if (int st = copy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost)) return st;
+        }
         return DSP_OK;
     }
 };
 
 // DSP_EXEC_SYNC / DSP_EXEC_HOST_BUFFERS: the call returns when its stream has finished
 int finish(const dsp_exec *ex);
+
+// A row call's device context: its device made current until it returns, its
+// stream and its staging.  `status` is the device's, tested once after
+// construction; done() is the call's ending, the outputs copied back and finish().
+struct RowCall {
+    const dsp_exec *const ex;
+    const DeviceGuard guard;
+    const int status, dev;
+    const hipStream_t s;
+    Stage stage;
+    explicit RowCall(const dsp_exec *ex) : ex(ex), guard(ex), status(guard.status), dev(guard.dev), s(stream_of(ex)), stage(ex) {}
+    int done() { const int st = stage.copy_back(); return st ? st : finish(ex); }
+};
 
 // ---------------------------------------------------------------------------
 // channel groups: a kernel takes at most kMaxChannels row pointers

@@ -3,7 +3,7 @@
 // and analyses on the caller's stream (render_device, stft_device), and the
 // extern "C" calls built on them: dsp_render_*, dsp_stft_magnitude,
 // dsp_ir_analysis, dsp_biquad_plan, dsp_conv_plan.  What it shares with
-// capi.cpp and capi_signal.cpp is in capi_impl.hpp.
+// the C ABI's other files is in capi_impl.hpp.
 #include "capi_impl.hpp"
 
 namespace dspb {

@@ -10,7 +10,7 @@
 namespace dspb {
 
 constexpr uint32_t kDecayMaxBands = 32;
-constexpr uint32_t kDecayGroup = 16;  // rows per launch (kMaxChannels: capi_signal.cpp asserts it)
+constexpr uint32_t kDecayGroup = 16;  // rows per launch (kMaxChannels: capi_bigfft.cpp asserts it)
 // What a call's rows may hold of the scratch: the launches walk the (channel,
 // band) pairs in groups of rows = clamp(kDecayRowsBytes / row_bytes, 1, 16),
 // row_bytes = 8 n (the transform's two work buffers) + 2 (4 n + 8) (the

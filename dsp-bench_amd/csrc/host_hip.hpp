@@ -1,8 +1,11 @@
 // host_hip.hpp -- host-side idioms shared by the C ABI (capi.cpp,
-// capi_render.cpp, capi_signal.cpp) and the plugin module host (module*.cpp):
-// the device guard, the capture predicate and the row-overlap predicates.
+// capi_render.cpp, capi_rate.cpp, capi_bigfft.cpp, capi_grid.cpp) and the
+// plugin module host (module*.cpp): the device guard, the capture predicate,
+// the row-overlap predicates and a row call's layout rule.
 #pragma once
 #include "common.hpp"
+
+#include <initializer_list>
 
 #pragma GCC visibility push(hidden)
 namespace dspb {
@@ -68,6 +71,25 @@ inline bool rows_overlap_each_other(const Rows &a) {
     for (uint32_t i = 0; i < a.count; ++i)
         for (uint32_t j = i + 1; j < a.count; ++j)
             if (row_pair_overlaps(a.rows[i], a.floats, a.rows[j], a.floats)) return true;
+    return false;
+}
+
+// The layout rule of a row call, asked once per call: whether a row of an
+// output set overlaps a row of an input set, of another output set or of its
+// own set (input sets may share memory: they are only read).  Its exceptions:
+enum : uint32_t {
+    kInPlaceOk = 1,        // outs[0][c] == ins[0][c] (channel c in place) does not count
+    kOutputsUnchecked = 2  // the output sets are checked against the input sets only
+};
+inline bool output_rows_overlap(std::initializer_list<Rows> ins, std::initializer_list<Rows> outs, uint32_t except = 0) {
+    for (const Rows *o = outs.begin(); o != outs.end(); ++o) {
+        for (const Rows *i = ins.begin(); i != ins.end(); ++i)
+            if (rows_overlap(*i, *o, (except & kInPlaceOk) && i == ins.begin() && o == outs.begin())) return true;
+        if (except & kOutputsUnchecked) continue;
+        for (const Rows *p = outs.begin(); p != o; ++p)
+            if (rows_overlap(*p, *o)) return true;
+        if (rows_overlap_each_other(*o)) return true;
+    }
     return false;
 }
 

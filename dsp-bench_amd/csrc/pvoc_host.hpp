@@ -10,7 +10,7 @@
 
 namespace dspb {
 
-constexpr uint32_t kPvocGroup = 16;   // rows per channel group (kMaxChannels: capi_signal.cpp asserts it)
+constexpr uint32_t kPvocGroup = 16;   // rows per channel group (kMaxChannels: capi_grid.cpp asserts it)
 constexpr uint32_t kPvocChunk = 64;   // output frames a wavefront walks
 constexpr uint32_t kPvocChunkMin = 8, kPvocChunkMax = 4096;  // what DSP_DEBUG_PVOC_CHUNK may set instead
 constexpr double kPvocRateMin = 0.125, kPvocRateMax = 8.0;

@@ -11,7 +11,7 @@ namespace dspb {
 
 constexpr uint32_t kStftCxN = 8192;
 constexpr uint32_t kStftCxBins = kStftCxN / 2 + 1;  // 4097
-constexpr uint32_t kStftCxGroup = 16;               // rows per channel group (kMaxChannels: capi_signal.cpp asserts it)
+constexpr uint32_t kStftCxGroup = 16;               // rows per channel group (kMaxChannels: capi_grid.cpp asserts it)
 constexpr uint32_t kIstftMinHop = 512;              // at most 16 frames touch a sample
 constexpr uint64_t kIstftFrameBytes = 4ull * kStftCxN;  // a windowed inverse frame in the scratch
 // the frames a chunk may hold: chunk = the largest count with rows chunk 32 KiB

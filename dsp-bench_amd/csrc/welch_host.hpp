@@ -14,7 +14,7 @@ constexpr uint32_t kWelchN = 8192;
 constexpr uint32_t kWelchBins = kWelchN / 2 + 1;  // 4097
 constexpr uint32_t kWelchRun = 16;                // frames summed in float32 before float64 takes over
 constexpr uint32_t kWelchSpec4 = kConvSpec4;      // float4 per scratch spectrum (conv_fdl.hip's layout)
-constexpr uint32_t kWelchGroup = 16;              // rows per channel group (kMaxChannels: capi_signal.cpp asserts it)
+constexpr uint32_t kWelchGroup = 16;              // rows per channel group (kMaxChannels: capi_grid.cpp asserts it)
 // the spectra a chunk may hold: chunk = the largest multiple of kWelchRun with
 // rows chunk 33792 bytes <= this (rows = min(C, 16) + has_ref; at least one run)
 constexpr uint64_t kWelchSpectraBytes = 64ull << 20;
